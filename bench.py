@@ -24,7 +24,17 @@ cpu_baseline: the oracle restatement (oracle/cpu_baseline.py) compiled -O3 -marc
 cpp_face: the C++ host face (include/ldso_amd/energy_functional.h) timed as FullSystem drives it
           (ldso_amd/lib/ldso_face_bench, one S7 window) beside the C ABI's ldso_ba_optimize.
 
+A plain run does only what the headline needs: it loads the windows, warms up, times the K
+steps and prints the line (`value`, `ms_per_step`, the roofline of the timed region's own
+k_linearize events).  --full adds every other leg to the line: the per-kernel breakdown and
+`frac_step`, the steps without events, the batched GN iteration, single_window, s11,
+sharded_window (N > 1), tracker, cpp_face and the CPU baselines; a plain run leaves those keys null.
+--dump-outputs DIR writes what the last timed step left for its caller (energies, stitched
+systems, per-residual and per-point results of rank 0's windows) as DIR/<name>.npy, float32 or
+float64; the inputs are seeded, so two builds run with the same arguments compare array by array.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--windows B] [--mode replicas|shard]
+                       [--full] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -523,6 +533,65 @@ def sharded_window_leg(dist, rank, world, device, coll_dev, steps=20):
     return out
 
 
+DUMP_MAX_WINDOWS = 64        # stitched systems: at most this many windows (132 x 132 f64 at 16 frames)
+DUMP_MAX_RESIDUALS = 400000  # per-residual rows (68 B each as float32)
+DUMP_MAX_POINTS = 128000     # per-point rows (36 B each)
+
+
+def dump_sample(n, cap, seed):
+    """Every index below n, or a fixed seeded sample of `cap` of them in ascending order."""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=cap, replace=False))
+
+
+def dump_outputs(ctx, out_dir):
+    """What the last ldso_ba_linearize left for its caller, read back through the C ABI's getters
+    and written as out_dir/<name>.npy (float64 as the ABI returns it, everything else float32):
+    energy [B, 3], the stitched systems HA / bA / HL / bL / Hsc / bsc and frame_energy_th per window
+    (rows padded with zeros to the largest window), every per-residual field (res_*) and
+    per-point field (pt_*) with the windows concatenated in order.  Windows, residual rows and
+    point rows beyond the DUMP_MAX_* caps are a seeded sample that depends on the counts only, so
+    the files stay below 64 MB and hold the same rows from run to run."""
+    os.makedirs(out_dir, exist_ok=True)
+    B = len(ctx.windows)
+    wins = dump_sample(B, DUMP_MAX_WINDOWS, 1)
+    dim = max(ctx.windows[i].dim for i in wins)
+    nf = max(ctx.windows[i].n_frames for i in wins)
+    arrays = {"energy": np.stack([ctx.energy(int(i)) for i in wins])}
+    for k in ("HA", "HL", "Hsc"):
+        arrays[k] = np.zeros((len(wins), dim, dim), np.float64)
+    for k in ("bA", "bL", "bsc"):
+        arrays[k] = np.zeros((len(wins), dim), np.float64)
+    arrays["frame_energy_th"] = np.zeros((len(wins), nf), np.float32)
+    for j, i in enumerate(wins):
+        s = ctx.system(int(i))
+        n = ctx.windows[i].dim
+        for k, v in s.items():
+            arrays[k][(j,) + (slice(0, n),) * v.ndim] = v
+        arrays["frame_energy_th"][j, :ctx.windows[i].n_frames] = ctx.frame_energy_th(int(i))
+    for prefix, getter, count, cap, seed in (("res_", ctx.residuals, "n_residuals", DUMP_MAX_RESIDUALS, 2),
+                                             ("pt_", ctx.points, "n_points", DUMP_MAX_POINTS, 3)):
+        counts = [getattr(w, count) for w in ctx.windows]
+        rows = dump_sample(sum(counts), cap, seed)
+        starts = np.concatenate([[0], np.cumsum(counts)])
+        parts = {}
+        for i in range(B):
+            mine = rows[(rows >= starts[i]) & (rows < starts[i + 1])] - starts[i]
+            if mine.size:
+                for k, v in getter(i).items():
+                    parts.setdefault(k, []).append(v[mine].astype(np.float32))
+        for k, v in parts.items():
+            arrays[prefix + k] = np.concatenate(v)
+    total = 0
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+        total += v.nbytes
+    assert total <= 64 * 2 ** 20, total
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -537,6 +606,11 @@ def main():
     ap.add_argument("--no-tracker", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the S11 line")
     ap.add_argument("--no-shard-leg", action="store_true", help="N > 1: skip the sharded S11 window")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every other leg (kernel breakdown, GN iteration, single "
+                         "window, S11, sharded window, tracker, C++ face, CPU baselines); the --no-* options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
 
     world, launched = world_from_env(args.gpus)
@@ -619,24 +693,29 @@ def main():
     # host-side download leaves the GPU idle between the warmup and the timed steps
     n_gather = sum(int((ctx.residuals(i)["state"] != 1).sum()) for i in range(len(windows)))
     ctx.set_kernel_timing(False)
-    # the same steps without the roofline's event pair (each costs the stream ~5 us of idle GPU on
-    # either side of k_linearize): reported beside the headline, never as it
-    ctx.sync()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    ctx.sync()
-    ms_step_no_events = 1e3 * (time.perf_counter() - t0) / args.steps
-    ctx.set_tuning(7, -1)
-    ctx.set_kernel_timing(True)  # breakdown of every kernel, outside the timed region
-    for _ in range(min(args.steps, 20)):
-        step()
-    ctx.sync()
-    kall = ctx.kernel_times()
-    ctx.set_kernel_timing(False)
+    if args.dump_outputs and rank == 0:  # the last timed step's results, before anything else runs
+        dump_outputs(ctx, args.dump_outputs)
+    ms_step_no_events = None
+    kall = {}
+    if args.full:
+        # the same steps without the roofline's event pair (each costs the stream ~5 us of idle GPU on
+        # either side of k_linearize): reported beside the headline, never as it
+        ctx.sync()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        ctx.sync()
+        ms_step_no_events = 1e3 * (time.perf_counter() - t0) / args.steps
+        ctx.set_tuning(7, -1)
+        ctx.set_kernel_timing(True)  # breakdown of every kernel, outside the timed region
+        for _ in range(min(args.steps, 20)):
+            step()
+        ctx.sync()
+        kall = ctx.kernel_times()
+        ctx.set_kernel_timing(False)
     # every resident window through a full device GN iteration (pass + solve + resubstitute)
     gn = None
-    if args.mode == "replicas" and max(w.n_frames for w in windows) <= 11:
+    if args.full and args.mode == "replicas" and max(w.n_frames for w in windows) <= 11:
         nss = [w.nullspaces() for w in windows]
         for _ in range(3):
             ctx.iterate(2, 1e-5, nss, fetch_steps=False)
@@ -677,13 +756,13 @@ def main():
 
     # N > 1: one S11 window sharded over every rank, the library's RCCL exchange in each pass
     sharded = None
-    if dist is not None and not args.no_shard_leg:
+    if args.full and dist is not None and not args.no_shard_leg:
         sharded = sharded_window_leg(dist, rank, world, local_rank, coll_dev, steps=min(args.steps, 20))
 
     # one window: pass alone, and a GN iteration with the solve on the host (stitched-system
     # download + LDLT + resubstitute) or on the device (ldso_ba_iterate), host clock
     single = None
-    if rank == 0:
+    if args.full and rank == 0:
         sw = synth.make_window(n_frames=N, n_points=P, seed=1)
         ns = sw.nullspaces()
         c1 = BAContext(local_rank)
@@ -728,19 +807,19 @@ def main():
         c1.close()
 
     s11 = None
-    if rank == 0 and args.mode == "replicas" and not args.no_secondary:
+    if args.full and rank == 0 and args.mode == "replicas" and not args.no_secondary:
         s11 = secondary_s11(local_rank)
 
     tracker = None
-    if rank == 0 and not args.no_tracker:
+    if args.full and rank == 0 and not args.no_tracker:
         tracker = tracker_leg(local_rank, with_cpu=(world == 1 and not args.no_cpu))
         tracker["trace_new_coarse"] = trace_leg(local_rank, with_cpu=(world == 1 and not args.no_cpu))
         tracker["activate_points"] = activation_leg(local_rank, with_cpu=(world == 1 and not args.no_cpu))
 
-    face = cpp_face_leg() if rank == 0 else None
+    face = cpp_face_leg() if args.full and rank == 0 else None
 
     cpu = cpu1 = cpu6 = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cb = cpu_baseline(args.cpu_seconds)
         if cb:
             cpu, cpu1, cpu6 = cb.get("batched"), cb["socket_pinned"], cb["six_threads"]
@@ -762,6 +841,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": ms_step,
             "higher_is_better": True,
             "scaling": "weak" if args.mode == "replicas" else "strong",
