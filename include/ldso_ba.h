@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define LDSO_BA_ABI_VERSION 6
+#define LDSO_BA_ABI_VERSION 7
 
 #define LDSO_BA_PATTERN_NUM 8      /* patternNum, Settings.h:225 (staticPattern[8])     */
 #define LDSO_BA_CPARS 4            /* CPARS, NumTypes.h:25                              */
@@ -502,6 +502,14 @@ int ldso_ba_optimize(ldso_ba_ctx *ctx, int32_t n_its, const ldso_ba_opt_settings
                      const ldso_ba_frame_state *frames, const double *calib_value, const double *calib_value_zero,
                      const double *ns, double *energy_out, ldso_ba_frame_state *frames_out, double *calib_out,
                      float *idepth_out, int32_t *iterations_out, int32_t *status_out);
+
+/* A read-only view of the loop's state for window win, as the device buffers stand (a copy after
+ * the stream has drained; no kernel runs).  Outputs (any may be NULL): x [8N+4] the last solve's
+ * x (undefined before the first device solve); precalc [N*N][LDSO_BA_PRECALC_STRIDE] the
+ * FrameFramePrecalc rows the next pass reads (the loaded ones, or those of ldso_ba_optimize's last
+ * step); prior [8N+4][2] the solver's prior vector as (HL diagonal, bL) pairs: prior and
+ * prior * delta_prior per frame parameter, cPrior and cPrior * cDeltaF for the calibration. */
+int ldso_ba_get_loop_state(ldso_ba_ctx *ctx, int32_t win, double *x, float *precalc, double *prior);
 
 /* doStepFromBackup's frame and calibration step on the host (the same se3.h statements as the
  * device loop): out[f] = in[f] stepped by -x[4 + 8f ..]; calib_value (if not NULL) += -x[0..3],

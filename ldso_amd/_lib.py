@@ -45,7 +45,7 @@ FRAME_STATE_DTYPE = np.dtype(
 assert FRAME_STATE_DTYPE.itemsize == 272
 
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 # setting_solverMode bits (Settings.h:14-25) and ldso_ba_optimize's per-window outcome
 SOLVER_SVD, SOLVER_ORTHOGONALIZE_SYSTEM, SOLVER_ORTHOGONALIZE_POINTMARG, SOLVER_ORTHOGONALIZE_FULL = 1, 2, 4, 8
@@ -188,6 +188,7 @@ ABI = [
     ("ldso_ba_get_settings", C.c_int, [C.c_void_p, C.c_void_p]),
     ("ldso_ba_optimize", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, f64p, f64p, f64p, f64p, C.c_void_p,
                                    f64p, f32p, i32p, i32p]),
+    ("ldso_ba_get_loop_state", C.c_int, [C.c_void_p, C.c_int32, f64p, f32p, f64p]),
     ("ldso_ba_frame_step", C.c_int, [C.c_int32, C.c_void_p, f64p, C.c_void_p, f64p, f64p, f32p, f32p]),
     ("ldso_ba_step_canbreak", C.c_int, [C.c_int32, f64p, C.c_float, C.c_float, C.c_float, i32p]),
     ("ldso_ba_set_kernel_timing", C.c_int, [C.c_void_p, C.c_int32]),

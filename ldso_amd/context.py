@@ -90,6 +90,19 @@ class BAContext:
                                            L.ptr(status, L.i32p)))
         return e, fo, co, self._split(idep, [w.n_points for w in self.windows]), its, status
 
+    def loop_state(self, win: int = 0) -> dict:
+        """ldso_ba_get_loop_state: the device loop's buffers of window `win` as they stand -- x [8N+4]
+        (the last device solve), precalc [N*N][PRECALC_STRIDE], prior [8N+4][2] (HL diagonal, bL)."""
+        if not 0 <= win < len(self.windows):  # refused by the library, with its message
+            L.check(self._lib.ldso_ba_get_loop_state(self._h, int(win), L.ptr(None, L.f64p), L.ptr(None, L.f32p),
+                                                     L.ptr(None, L.f64p)))
+        N = self.windows[win].n_frames
+        o = dict(x=np.zeros(8 * N + 4, np.float64), precalc=np.zeros((N * N, L.PRECALC_STRIDE), np.float32),
+                 prior=np.zeros((8 * N + 4, 2), np.float64))
+        L.check(self._lib.ldso_ba_get_loop_state(self._h, int(win), L.ptr(o["x"], L.f64p), L.ptr(o["precalc"], L.f32p),
+                                                 L.ptr(o["prior"], L.f64p)))
+        return o
+
     def comm_init(self, unique_id, rank: int, world: int):
         """Attach to an RCCL communicator (ldso_ba_comm_init); unique_id: 128 bytes from
         ldso_ba_comm_unique_id on rank 0.  See ldso_amd.dist.attach_rccl."""

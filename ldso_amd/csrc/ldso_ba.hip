@@ -6740,6 +6740,24 @@ int ldso_ba_optimize(ldso_ba_ctx *c, int32_t n_its, const ldso_ba_opt_settings *
     return 0;
 }
 
+int ldso_ba_get_loop_state(ldso_ba_ctx *c, int32_t win, double *x, float *precalc, double *prior) {
+    if (!c) return fail(-1, "null ctx");
+    if (c->n_win == 0) return fail(-1, "no windows loaded");
+    if (win < 0 || win >= c->n_win) return fail(-1, "bad window index");
+    if (!c->d_x.p || !c->d_precalc.p || !c->d_prior.p) return fail(-1, "this context holds no loop state");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = ldso_ba_sync(c);
+    if (rc) return rc;
+    const WinDev &D = c->wd[win];
+    const size_t dim = (size_t)8 * D.N + 4, pairs = (size_t)D.N * D.N;
+    if (x) HIP_TRY(hipMemcpy(x, c->d_x.p + D.vec_base, dim * sizeof(double), hipMemcpyDeviceToHost));
+    if (precalc)
+        HIP_TRY(hipMemcpy(precalc, c->d_precalc.p + (size_t)D.pair_base * LDSO_BA_PRECALC_STRIDE,
+                          pairs * LDSO_BA_PRECALC_STRIDE * sizeof(float), hipMemcpyDeviceToHost));
+    if (prior) HIP_TRY(hipMemcpy(prior, c->d_prior.p + (size_t)2 * D.vec_base, 2 * dim * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int ldso_ba_frame_step(int32_t n, const ldso_ba_frame_state *in, const double *x, ldso_ba_frame_state *out,
                        double *calib_value, const double *calib_value_zero, float *calib_scaled_out,
                        float *c_delta_out) {

@@ -11,6 +11,9 @@
 // quaternion norm as (x^2 + z^2) + (y^2 + w^2)); where the reference build fuses a multiply-add
 // through Eigen's pmadd the result differs by an ulp.  The ABI hands worldToCam_evalPT over as
 // matrix3x4(); it becomes a quaternion again through Eigen's Quaternion(Matrix3) as SE3(R, t) does.
+// The reference keeps that quaternion and never makes the round trip, so q(R(q)) can differ from
+// its quaternion in the last bits: bit-exactness with Sophus ends at the matrix ABI boundary
+// (eval_pose), and every PRE_worldToCam inherits that.
 // Also here: FrameHessian::setState's PRE_worldToCam (FrameHessian.h:95-114),
 // AffLight::fromToVecExposure (AffLight.h:27-35), the per-pair body of FrameFramePrecalc::Set
 // (FrameFramePrecalc.cc:6-35) and FrameHessian::takeData (FrameHessian.cc:131-135, FrameHessian.h:
@@ -212,7 +215,10 @@ struct Pose {  // Sophus SE3: x -> R(q) x + t
         } else {
             double st, ct;
             sin_cos(theta, st, ct);
-            const double s1 = (1.0 - ct) / theta_sq, s2 = (theta - st) / (theta_sq * theta);
+            // se3.hpp:780 declares a new theta_sq = theta * theta here; fl(sqrt(x))^2 is often not
+            // x, so expAndTheta's squaredNorm above is not reused
+            const double theta_sq_v = theta * theta;
+            const double s1 = (1.0 - ct) / theta_sq_v, s2 = (theta - st) / (theta_sq_v * theta);
             for (int k = 0; k < 9; k++) V.m[k] = ((k % 4 == 0 ? 1.0 : 0.0) + s1 * W.m[k]) + s2 * W2.m[k];
         }
         mat_vec(V, a, p.t);
@@ -273,11 +279,23 @@ LDSO_HD inline Pose current_pose(const ldso_ba_frame_state &f) {
     for (int i = 0; i < 6; i++) eps[i] = (i < 3 ? kScaleXiTrans : kScaleXiRot) * f.state[i];
     return Pose::exp(eps) * eval_pose(f);
 }
+// the reference's float exp: on the host libm's expf, which glibc keeps within 0.502 ulp, i.e.
+// correctly rounded for nearly every argument; on the device the double exp rounded once to float,
+// which is that same float (the device library's expf is only within an ulp: it moved
+// PRE_aff_mode's a by an ulp in some pairs and, through the rounded product a * bF, b by four of
+// its own)
+LDSO_HD inline float exp_float(float x) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return (float)exp((double)x);
+#else
+    return expf(x);
+#endif
+}
 // AffLight::fromToVecExposure (include/AffLight.h:27-35), float arithmetic as in the reference
 LDSO_HD inline void affine_from_to(float expF, float expT, float aF, float bF, float aT, float bT, float &a, float &b) {
 #pragma clang fp contract(off)
     if (expF == 0 || expT == 0) expF = expT = 1;
-    a = expf(aT - aF) * expT / expF;
+    a = exp_float(aT - aF) * expT / expF;
     b = bT - a * bF;
 }
 

@@ -1301,7 +1301,8 @@ SE3d se3_exp(const double a[6]) {
         double W[9], W2[9];
         hat(w, W);
         mm3(W, W, W2);
-        const double B = (1 - std::cos(th)) / th2, C = (th - std::sin(th)) / (th2 * th);
+        const double thv2 = th * th;  // se3.hpp:780: a new theta_sq = theta * theta, not squaredNorm
+        const double B = (1 - std::cos(th)) / thv2, C = (th - std::sin(th)) / (thv2 * th);
         for (int i = 0; i < 9; i++) V[i] = ((i % 4 == 0) ? 1.0 : 0.0) + B * W[i] + C * W2[i];
     }
     mv3(V, up, T.t);

@@ -16,6 +16,10 @@ host loop's (x is sensitive to 1e-6 changes of H along the near-gauge directions
 projected out from iteration 2 on: test_gpu_parity's sensitivity envelope); iteration counts and
 exit statuses EQUAL.  The windows are chosen with the canbreak criterion at least 20 % away from
 its threshold at every iteration (the ratios are printed), so the reassociation cannot flip it.
+
+These are the bars of a free-running comparison, and they are not the only check of the loop:
+test_optimize_lockstep.py walks the oracle beside the device and puts it back onto the device's own
+state after every step, which pins each frame step, precalc row, prior and point step by itself.
 """
 import ctypes as C
 

@@ -10,8 +10,12 @@ the math module), pins both:
   * the product's host helpers through the C ABI -- ldso_ba_frame_step (doStepFromBackup's
     log(exp(step) exp(state))), ldso_ba_frame_take_data (get_state_minus_stateZero),
     ldso_ba_set_adjoints (-Adj^T of target * host^-1) and ldso_ba_frame_precalc (the float
-    rotation matrices of leftToLeft_0 and leftToLeft) -- to at most 4 ulp (measured: 0);
-  * the oracle's doStepFromBackup states equal the product's.
+    rotation matrices of leftToLeft_0 and leftToLeft) -- at 0 ulp: the host path calls the same
+    glibc sin / cos / atan as the math module;
+  * the oracle's doStepFromBackup states equal the product's;
+  * known answers on which se3.hpp:780's theta_sq = theta * theta and expAndTheta's squaredNorm
+    give different bits (test_exp_theta_sq_known_answers): the three restatements once shared the
+    second form and agreed with each other, not with Sophus.
 Parity unpinned by the reference binary itself (Eigen is absent here): the reference
 build may fuse a multiply-add where Eigen's packet code uses pmadd.
 """
@@ -97,7 +101,11 @@ def mv(A, v):
     return tuple((A[i][0] * v[0] + A[i][1] * v[1]) + A[i][2] * v[2] for i in range(3))
 
 
-def se3_exp(a):  # SE3::exp (se3.hpp:765-786) with SO3::expAndTheta (so3.hpp:577-605)
+def se3_exp(a, foil=False):  # SE3::exp (se3.hpp:765-786) with SO3::expAndTheta (so3.hpp:577-605)
+    """foil=True: V's factors from expAndTheta's squaredNorm instead of se3.hpp:780's new
+    theta_sq = theta * theta -- the substitution this file, se3.h and the oracle once shared.
+    fl(sqrt(x))^2 is often not x, so the two differ; test_exp_theta_sq_known_answers keeps it as
+    the wrong answer the product must not give."""
     w = a[3:]
     theta_sq = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]
     theta = math.sqrt(theta_sq)
@@ -114,8 +122,9 @@ def se3_exp(a):  # SE3::exp (se3.hpp:765-786) with SO3::expAndTheta (so3.hpp:577
     if theta < EPS:
         V = q_matrix(q)
     else:
-        s1 = (1.0 - math.cos(theta)) / theta_sq
-        s2 = (theta - math.sin(theta)) / (theta_sq * theta)
+        theta_sq_v = theta_sq if foil else theta * theta  # se3.hpp:780: Scalar theta_sq = theta * theta
+        s1 = (1.0 - math.cos(theta)) / theta_sq_v
+        s2 = (theta - math.sin(theta)) / (theta_sq_v * theta)
         V = [[((1.0 if i == j else 0.0) + s1 * W[i][j]) + s2 * W2[i][j] for j in range(3)] for i in range(3)]
     return q, mv(V, a[:3])
 
@@ -255,7 +264,7 @@ def test_frame_step_follows_sophus(built, seed):
         ref = se3_log(se3_mul(se3_exp(step), se3_exp(tuple(float(v) for v in fr["state"][f, :6]))))
         worst = max(worst, ulps(out["state"][f, :6], ref))
     print("frame step: max ulp vs the Python Sophus restatement", worst)
-    assert worst <= 4
+    assert worst == 0
     o_fr = oracle.do_step_from_backup(fr, x, cval.copy(), cval.copy(), w.point_host, w.point_data[:, 2],
                                       np.zeros(w.n_points, np.float32))[0]
     np.testing.assert_array_equal(o_fr["state"], out["state"])
@@ -286,7 +295,7 @@ def test_take_data_adjoints_and_precalc_follow_sophus(built):
             got = adH[h + N * t].reshape(8, 8)[:6, :6]
             worst = max(worst, ulps(got, (-A.T) * rs[:, None]))
     print("takeData / adjoints: max ulp", worst)
-    assert worst <= 4
+    assert worst == 0
     # FrameFramePrecalc::Set's float rotations (FrameFramePrecalc.cc:12-18), PRE_worldToCam =
     # exp(w2c_leftEps) * evalPT (FrameHessian.h:95-114)
     pre = np.zeros((N * N, L.PRECALC_STRIDE), np.float32)
@@ -310,3 +319,90 @@ def test_take_data_adjoints_and_precalc_follow_sophus(built):
     np.testing.assert_array_equal(t_or["precalc"], pre)
     np.testing.assert_array_equal(t_or["ad_host"], adH)
     np.testing.assert_array_equal(t_or["frame_delta"], delta)
+
+
+# ------------------------------------------------------------------------------------------
+# se3.hpp:780: V's factors come from a new theta_sq = theta * theta, not from squaredNorm
+# ------------------------------------------------------------------------------------------
+def _step_log(step, state, foil):
+    return se3_log(se3_mul(se3_exp(step, foil), se3_exp(state, foil)))
+
+
+def theta_sq_cases():
+    """(step, state) pairs on which Sophus's text and the foil (se3_exp(foil=True)) give different
+    bits, chosen with the Python alone: the translation of exp(step) differs and so does the final
+    log(exp(step) exp(state)).  24 from a seeded draw over the scales 1e-6 ... 1, one more with
+    |omega| just below pi; `same` holds an omega below the 1e-10 branch (V = so3.matrix(): both
+    variants are one code path) and a zero step."""
+    rng = np.random.default_rng(20)
+    differ = []
+    while len(differ) < 24:
+        scale = 10.0 ** rng.uniform(-6, 0)
+        step = tuple(float(v) for v in rng.standard_normal(6) * scale)
+        state = tuple(float(v) for v in rng.standard_normal(6) * 10.0 ** rng.uniform(-6, 0))
+        if len(differ) < 8 and se3_log(se3_exp(state)) == se3_log(se3_exp(state, True)):
+            continue  # the first 8 also separate takeData's delta_prior = log(exp(state))
+        if se3_exp(step)[1] != se3_exp(step, True)[1] and _step_log(step, state, False) != _step_log(step, state, True):
+            differ.append((step, state))
+    while len(differ) < 25:  # theta near pi
+        d = rng.standard_normal(3)
+        om = d / np.linalg.norm(d) * (math.pi - 1e-3 * rng.uniform(0.1, 1))
+        step = tuple(float(v) for v in rng.standard_normal(3)) + tuple(float(v) for v in om)
+        state = tuple(float(v) for v in rng.standard_normal(6) * 0.01)
+        th = math.sqrt((step[3] * step[3] + step[4] * step[4]) + step[5] * step[5])
+        if (3.14 < th < math.pi and se3_exp(step)[1] != se3_exp(step, True)[1]
+                and _step_log(step, state, False) != _step_log(step, state, True)):
+            differ.append((step, state))
+    same = [((0.3, -0.2, 0.1, 3e-11, -4e-11, 5e-11), differ[0][1]), ((0.0,) * 6, differ[1][1])]
+    return differ, same
+
+
+def test_exp_theta_sq_known_answers(built):
+    """Pose::exp (ldso_ba_frame_step, ldso_ba_frame_take_data) and the oracle's se3_exp
+    (do_step_from_backup) give Sophus's bits -- 0 ulp against the Python restatement of the text, the
+    same glibc sin / cos / atan on both sides -- on inputs where reusing squaredNorm for V's
+    theta_sq (the foil) gives other bits, so either side falling back to the foil fails here."""
+    differ, same = theta_sq_cases()
+    assert len(differ) >= 21
+    for step, state in differ:  # the power of the test, from the Python alone
+        assert se3_exp(step)[1] != se3_exp(step, True)[1]
+        assert _step_log(step, state, False) != _step_log(step, state, True)
+    assert any(math.sqrt(sum(v * v for v in s[3:])) < EPS and any(s[3:]) for s, _ in same)
+    assert any(3.14 < math.sqrt(sum(v * v for v in s[3:])) < math.pi for s, _ in differ)
+    cases = differ + same
+    lib = L.lib()
+    n_dprior_differs = 0
+    for c0 in range(0, len(cases), L.MAX_FRAMES):
+        chunk = cases[c0:c0 + L.MAX_FRAMES]
+        N = len(chunk)
+        fr = np.zeros(N, L.FRAME_STATE_DTYPE)
+        fr["world_to_cam_evalpt"][:, [0, 4, 8]] = 1.0
+        fr["ab_exposure"] = 1.0
+        x = np.zeros(8 * N + 4)
+        for f, (step, state) in enumerate(chunk):
+            fr["state"][f, :6] = state
+            fr["state_zero"][f, :6] = [-v for v in step]  # takeData's exp(-state_zero) = exp(step)
+            x[4 + 8 * f:4 + 8 * f + 6] = [-v for v in step]  # the step is 1.0 * -x
+        out = np.zeros_like(fr)
+        L.check(lib.ldso_ba_frame_step(N, fr.ctypes.data, L.ptr(x, L.f64p), out.ctypes.data, L.ptr(None, L.f64p),
+                                       L.ptr(None, L.f64p), L.ptr(None, L.f32p), L.ptr(None, L.f32p)))
+        delta, dprior = np.zeros((N, 8)), np.zeros((N, 8))
+        L.check(lib.ldso_ba_frame_take_data(N, fr.ctypes.data, None, L.ptr(None, L.f64p), L.ptr(delta, L.f64p),
+                                            L.ptr(dprior, L.f64p)))
+        cval = np.full(4, 1.0)
+        o_fr = oracle.do_step_from_backup(fr, x, cval.copy(), cval.copy(), np.zeros(0, np.int32), np.zeros(0, np.float32),
+                                          np.zeros(0, np.float32))[0]
+        for f, (step, state) in enumerate(chunk):
+            ref, foil = _step_log(step, state, False), _step_log(step, state, True)
+            ref_p, foil_p = se3_log(se3_exp(state)), se3_log(se3_exp(state, True))
+            for name, got in (("ldso_ba_frame_step", out["state"][f, :6]), ("take_data delta", delta[f, :6]),
+                              ("oracle do_step_from_backup", o_fr["state"][f, :6])):
+                assert ulps(got, ref) == 0, (name, c0 + f, ulps(got, ref))
+                if (step, state) in differ:
+                    assert ulps(got, foil) > 0, (name, c0 + f, "equals the squaredNorm foil")
+            assert ulps(dprior[f, :6], ref_p) == 0, ("take_data delta_prior", c0 + f)
+            if ref_p != foil_p:
+                n_dprior_differs += 1
+                assert ulps(dprior[f, :6], foil_p) > 0, ("take_data delta_prior", c0 + f, "equals the foil")
+    print("delta_prior: states on which the foil differs", n_dprior_differs)
+    assert n_dprior_differs >= 8
