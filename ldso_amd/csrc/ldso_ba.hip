@@ -50,6 +50,7 @@
 
 #include "../../include/ldso_ba.h"
 #include "../../include/ldso_ct.h"
+#include "layout.h"
 #include "ldso_ba_internal.h"
 #include "se3.h"
 
@@ -59,56 +60,43 @@ namespace {
 
 constexpr int kWave = 64;
 constexpr int kTopVals = 96;    // 55 + 30 + 6 AccumulatorApprox entries, padded to 96
-constexpr int kMaxRes = LDSO_BA_MAX_FRAMES - 1;
 constexpr int kNumKernels = 8;
 const char *kKernelNames[kNumKernels] = {"k_linearize", "k_point_sc", "k_stitch",   "k_resubstitute",
                                          "k_frame_th",  "k_solve",    "k_activate", "k_stitch_sum"};
 
-thread_local std::string g_err;
-int fail(int code, const std::string &msg) {
-    g_err = msg;
-    return code;
-}
+inline int fail(int code, const std::string &msg) { return set_error(code, msg); }
 
-}  // namespace
-
-namespace ldso_ba {
-int set_error(int code, const std::string &msg) { return fail(code, msg); }
-}  // namespace ldso_ba
-
-namespace {
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \
         if (e_ != hipSuccess) return fail(-2, std::string(#expr) + ": " + hipGetErrorString(e_));  \
     } while (0)
 
-// Per-window device descriptor.
-struct WinDev {
-    int N, P, R, D;
-    int frame_base, pair_base, point_base, res_base;
-    int top_item_base, n_top_items;
-    int sc_item_base, n_sc_items;
-    int K, KP, ntiles, p_all;  // p_all: the window's points over every shard (numID)
-    long long sc_slab_base;  // floats
-    long long sys_base;      // doubles: packed system
-    long long stage_base;    // doubles: k_stitch contribution records, N^2 pairs x stage_rec(N)
-    int newest_begin, newest_end;
-    int rec_base;            // record slots: rec_base + s * P + q (s = target slot of host's point q)
-    int vec_base;            // per-window (8N+4)-vectors (priors, x): vec_base + i
-    int width, height;
-    float wM3, hM3;
-    float calib[4];
-    float cdelta[4];         // EnergyFunctional::cDeltaF (marginalisation pass only)
-};
+// Per-window device descriptor: the fields of layout.h's WinDesc under the name (and in the
+// namespace) the kernels' symbols have always carried.
+struct WinDev : WinDesc {};
+static_assert(sizeof(WinDev) == sizeof(WinDesc), "WinDev adds nothing to WinDesc");
+static_assert(sizeof(Item4) == sizeof(int4) && alignof(Item4) == alignof(int4) && sizeof(Item2) == sizeof(int2),
+              "layout.h's work items are the kernels' int4 / int2");
 
-// a debugging / A-B switch from the environment: set and not "0"
-inline bool getenv_flag(const char *name) {
-    const char *v = std::getenv(name);
-    return v && *v && !(v[0] == '0' && v[1] == 0);
+// The environment switches ("environment"): debugging / A-B aids, read here and
+// nowhere else.  A flag is on when set and not "0".
+struct Switches {
+    bool stitch_records;  // LDSO_BA_STITCH_RECORDS: k_stitch for every window size (read at load)
+    int hs_split;         // LDSO_BA_HS_SPLIT: -1 unset (by grid size), else 1 for "1...", 0 otherwise
+    bool solve_lds;       // LDSO_BA_SOLVE_LDS: the LDS solve k_solve
+    bool no_graph;        // LDSO_BA_NO_GRAPH: ldso_ba_optimize / _iterate launch directly
+    bool iterate_graph;   // LDSO_BA_ITERATE_GRAPH: ldso_ba_iterate replays a captured graph
+};
+Switches read_switches() {
+    auto flag = [](const char *name) {
+        const char *v = std::getenv(name);
+        return v && *v && !(v[0] == '0' && v[1] == 0);
+    };
+    const char *hs = std::getenv("LDSO_BA_HS_SPLIT");
+    return {flag("LDSO_BA_STITCH_RECORDS"), hs ? (hs[0] == '1' ? 1 : 0) : -1, flag("LDSO_BA_SOLVE_LDS"),
+            flag("LDSO_BA_NO_GRAPH"), flag("LDSO_BA_ITERATE_GRAPH")};
 }
-__host__ __device__ inline long long packed_len(int D) { return (long long)D * (D + 1) / 2; }
-__host__ __device__ inline long long sys_len(int D) { return 2 * (packed_len(D) + D); }
 
 // k_stitch's contribution record of one (h, t) pair (doubles): every term the reference's
 // stitchDouble adds for this pair, stored instead of accumulated, so that k_stitch_sum can add
@@ -121,7 +109,6 @@ __host__ __device__ inline long long sys_len(int D) { return 2 * (packed_len(D) 
 //        S6 accHcc / accbc [r * 5 + c] (only in the record of host i's first target)
 enum : int { kT1 = 0, kT2 = 64, kT3 = 128, kT4a = 192, kT4b = 224, kT5 = 256, kT6a = 272, kT6b = 280, kT7 = 288,
              kS1 = 292 };
-__host__ __device__ inline int stage_rec(int N) { return 520 + 64 * (N - 1); }
 __host__ __device__ inline int st_S2(int N) { return kS1 + 64 * (N - 1); }
 
 // ============================================================================================
@@ -1252,8 +1239,6 @@ __device__ void point_nid(const PointParams &P, int w, float *lds) {
 
 // points per k_point_sc block (one SYRK chunk partial).  128 (both waves gather, half the slab
 // partials) measured 28.5 vs 26.5 us with the stitch 0.8 us faster: the SYRK chains double (r4)
-constexpr int kScPoints = 64;
-constexpr int kPrePitch = 12;  // floats of staged precalc (R0, t0) per target in k_point_sc's LDS
 constexpr int kScThreads = 128;  // 2 waves: a lane per point gathers, both run the SYRK tiles
 static_assert(kScPoints <= kScThreads, "one gathering lane per point");
 // residual records per round trip (r4: 3 -> two round trips at N = 7, 27.6 vs 28.3 us; r5: 6 -> one round
@@ -4231,6 +4216,12 @@ template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() {  // a context's buffers go with it (ldso_ba_destroy)
+        if (p) release();
+    }
     int alloc(size_t count) {
         g_alloc_gen.fetch_add(1);
         if (p) (void)hipFree(p);
@@ -4253,19 +4244,6 @@ struct DevBuf {
         n = 0;
     }
     size_t bytes() const { return n * sizeof(T); }
-};
-
-struct WinHost {
-    int N, P, R;                    // this shard
-    int P_all, R_all;               // caller's counts
-    std::vector<int> pt_orig;       // sorted -> caller point index
-    std::vector<int> rs_orig;       // sorted -> caller residual index
-    std::vector<int> rs_slot;       // sorted residual -> record slot (global)
-    std::vector<int> pt_host;       // sorted point host
-    std::vector<double> c_prior, frame_prior, frame_delta_prior;
-    std::vector<float> c_delta;
-    std::vector<float> adHF, adTF;  // float adjoints (resubstitute)
-    bool add_priors = true;
 };
 
 struct PendingEv {
@@ -4356,6 +4334,7 @@ struct ldso_ba_ctx {
     bool host_stitch = false;
     int n_cu = 256;  // compute units (k_stitch_host splits its blocks when the grid fits at once)  // k_stitch_host + k_stitch_host_sum (every window <= kHostStitchMaxN keyframes)
     const float4 *img_ext = nullptr;
+    const float4 *images() const { return img_ext ? img_ext : d_img.p; }  // the frames the kernels read
     DevBuf<float> d_adhtd;  // [pairs][8] adHTdeltaF
     int vec_total = 0;
     size_t sc_smem_max = 0;
@@ -4520,74 +4499,38 @@ void drain_events(ldso_ba_ctx *c) {
     c->pending.clear();
 }
 
-// timed_launch for a launch that takes the events itself (hipExtLaunchKernelGGL's start / stop
-// events, stamped by the dispatch): the stream carries no event packets around the kernel, which
-// on this path cost ~5 us of idle GPU on each side of it
+// One launch into kernel-timing slot `slot`: when the slot is timed, two events from the pool are
+// handed to launch(a, b) and queued for drain_events; the launch's error becomes the call's.
+// record_on: the stream on which the events are recorded around the launch, or nullptr when the
+// launch stamps them itself.
 template <typename F>
-int timed_launch_ext(ldso_ba_ctx *c, int slot, hipStream_t st, F &&launch) {
+int timed_launch_events(ldso_ba_ctx *c, int slot, hipStream_t record_on, F &&launch) {
     hipEvent_t a = nullptr, b = nullptr;
     const bool timed = c->timing && ((c->timing_mask >> slot) & 1u);
     if (timed) {
         a = get_event(c);
         b = get_event(c);
+        if (record_on) (void)hipEventRecord(a, record_on);
     }
     launch(a, b);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(-2, std::string("launch ") + kKernelNames[slot] + ": " + hipGetErrorString(e));
-    if (timed) c->pending.push_back({slot, a, b});
-    (void)st;
-    return 0;
-}
-template <typename F>
-int timed_launch(ldso_ba_ctx *c, int slot, hipStream_t st, F &&launch) {
-    hipEvent_t a = nullptr, b = nullptr;
-    const bool timed = c->timing && ((c->timing_mask >> slot) & 1u);
     if (timed) {
-        a = get_event(c);
-        b = get_event(c);
-        (void)hipEventRecord(a, st);
-    }
-    launch();
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-2, std::string("launch ") + kKernelNames[slot] + ": " + hipGetErrorString(e));
-    if (timed) {
-        (void)hipEventRecord(b, st);
+        if (record_on) (void)hipEventRecord(b, record_on);
         c->pending.push_back({slot, a, b});
     }
     return 0;
 }
-
-int check_window(const ldso_ba_window &w, bool need_images = true) {
-    if (w.n_frames < 2 || w.n_frames > LDSO_BA_MAX_FRAMES) return fail(-1, "n_frames out of range [2,16]");
-    if (w.n_points < 0 || w.n_residuals < 0) return fail(-1, "negative counts");
-    if ((need_images && !w.dI) || !w.frame_energy_th || !w.precalc || !w.ad_host || !w.ad_target || !w.c_prior || !w.c_delta ||
-        !w.frame_prior || !w.frame_delta_prior)
-        return fail(-1, "null frame-level pointer");
-    if (w.n_points > 0 && (!w.point_host || !w.point_data || !w.point_res_begin))
-        return fail(-1, "null point pointer");
-    if (w.n_residuals > 0 && (!w.res_target || !w.res_state || !w.res_energy || !w.res_flags))
-        return fail(-1, "null residual pointer");
-    if (w.width < 8 || w.height < 8) return fail(-1, "image too small");
-    if (w.point_res_begin && (w.point_res_begin[0] != 0 || w.point_res_begin[w.n_points] != w.n_residuals))
-        return fail(-1, "point_res_begin must span [0, n_residuals]");
-    for (int p = 0; p < w.n_points; p++) {
-        const int h = w.point_host[p];
-        if (h < 0 || h >= w.n_frames) return fail(-1, "point_host out of range");
-        const int b = w.point_res_begin[p], e = w.point_res_begin[p + 1];
-        if (e < b || e - b > kMaxRes) return fail(-1, "a point has more than N-1 residuals");
-        unsigned seen = 0;
-        for (int k = b; k < e; k++) {
-            const int t = w.res_target[k];
-            if (t < 0 || t >= w.n_frames || t == h) return fail(-1, "res_target out of range or equal to host");
-            if (seen & (1u << t)) return fail(-1, "duplicate (point, target) residual");
-            seen |= 1u << t;
-        }
-    }
-    return 0;
+// timed_launch for a launch that takes the events itself (hipExtLaunchKernelGGL's start / stop
+// events, stamped by the dispatch): the stream carries no event packets around the kernel, which
+// on this path cost ~5 us of idle GPU on each side of it
+template <typename F>
+int timed_launch_ext(ldso_ba_ctx *c, int slot, F &&launch) {
+    return timed_launch_events(c, slot, nullptr, launch);
 }
-
-size_t sc_smem_bytes(int KP) {
-    return ((size_t)kScPoints * (KP + 4) + (size_t)LDSO_BA_MAX_FRAMES * kPrePitch) * sizeof(float);
+template <typename F>
+int timed_launch(ldso_ba_ctx *c, int slot, hipStream_t st, F &&launch) {
+    return timed_launch_events(c, slot, st, [&](hipEvent_t, hipEvent_t) { launch(); });
 }
 
 // frame geometry of the image layout (all strides in float4 units)
@@ -4667,7 +4610,7 @@ int upload_priors(ldso_ba_ctx *c, int win) {
 // where ldso_ba_optimize computes the step's sumNID: in extra blocks of k_solve_fast, beside the
 // factorisation; with an exact solve mode in leading blocks of the pass's k_point_sc, or, with a
 // communicator, in extra blocks of the exchange's k_frame_th
-inline bool nid_in_solve(const ldso_ba_ctx *c) { return !c->solve_exact && !getenv_flag("LDSO_BA_SOLVE_LDS"); }
+inline bool nid_in_solve(const ldso_ba_ctx *c, const Switches &sw) { return !c->solve_exact && !sw.solve_lds; }
 // the idepths the sumNID chain walks: the context's points, or with a communicator every rank's
 // run of the window from the last exchange's all-gather (the runs concatenated in rank order are
 // the unsharded host-frame order, so the chain is the single-GPU one bit for bit)
@@ -4683,6 +4626,92 @@ NidSrc nid_source(const ldso_ba_ctx *c) {
         n.prun = (int)c->x_prun;
     }
     return n;
+}
+// k_linearize over every top item on the context's own residual state and records, outside any
+// optimize() loop (pass 0, no loop exits), fix and accumulate off: the callers set what differs
+LinParams lin_params(const ldso_ba_ctx *c) {
+    LinParams L{};
+    L.items = c->d_top_items.p;
+    L.wins = c->d_wins.p;
+    L.img = c->images();
+    L.ad_ht_delta = c->marg ? c->d_adhtd.p : nullptr;
+    L.precalc = c->d_precalc.p;
+    L.frame_th = c->d_frame_th.p;
+    L.rs_slot = c->d_rs_slot.p;
+    L.pt_data = c->d_pt_data.p;
+    L.rs_state = c->d_rs_state.p;
+    L.rs_newstate = c->d_rs_newstate.p;
+    L.rs_flags = c->d_rs_flags.p;
+    L.rs_energy = c->d_rs_energy.p;
+    L.rs_newenergy = c->d_rs_newenergy.p;
+    L.rs_energy_wo = c->d_rs_energy_wo.p;
+    L.rs_center = reinterpret_cast<float *>(c->d_rs_center.p);
+    L.center_stride = c->R_tot;
+    L.rec_a = c->d_rec_a.p;
+    L.rec_b = c->d_rec_b.p;
+    L.geo_snap = c->d_geo_snap.p;
+    L.top_slab = c->d_top_slab.p;
+    L.item_energy = c->d_item_energy.p;
+    L.frame_stride = c->frame_stride;
+    L.tiles_per_row = c->tiles_per_row;
+    L.aff_fix = aff_fix_bits(c);
+    L.item_base = 0;
+    L.n_items = c->n_top_items;
+    L.n_blocks = (L.n_items + 3) / 4;
+    return L;
+}
+// k_point_sc over every sc item (no sumNID blocks, no loop exits)
+PointParams point_params(const ldso_ba_ctx *c) {
+    PointParams Pp{};
+    Pp.items = c->d_sc_items.p;
+    Pp.wins = c->d_wins.p;
+    Pp.pt_data = c->d_pt_data.p;
+    Pp.pt_nres = c->d_pt_nres.p;
+    Pp.pt_tgt = c->d_pt_tgt.p;
+    Pp.rec_a = c->d_rec_a.p;
+    Pp.rec_b = c->d_rec_b.p;
+    Pp.precalc = c->d_precalc.p;
+    Pp.pt_out = c->d_pt_out.p;
+    Pp.sc_slab = c->d_sc_slab.p;
+    Pp.shift_prior = c->marg ? 0 : 1;
+    Pp.item_base = 0;
+    Pp.n_items = c->n_sc_items;
+    return Pp;
+}
+// either stitch over every window; the caller sets accumulate, the loop fields, hs_split and th_cap
+StitchParams stitch_params(const ldso_ba_ctx *c) {
+    StitchParams Sp{};
+    Sp.wins = c->d_wins.p;
+    Sp.pair_win = c->d_pair_win.p;
+    Sp.e_wo = c->d_rs_energy_wo.p;
+    Sp.frame_th = c->d_frame_th.p;
+    Sp.pair_items = c->d_pair_items.p;
+    Sp.top_slab = c->d_top_slab.p;
+    Sp.item_energy = c->d_item_energy.p;
+    Sp.host_items = c->d_host_items.p;
+    Sp.sc_slab = c->d_sc_slab.p;
+    Sp.adH = c->d_adH.p;
+    Sp.adT = c->d_adT.p;
+    Sp.sys = c->d_sys.p;
+    Sp.stage = c->d_stage.p;
+    Sp.win_energy = c->win_energy();
+    Sp.pair_base = 0;
+    Sp.win_base = 0;
+    Sp.n_win = c->n_win;
+    Sp.frame_win = c->d_frame_win.p;
+    Sp.frame_base = 0;
+    return Sp;
+}
+// a per-point value of every window from device order into the caller's: windows back to back,
+// each in its caller point order
+void scatter_points(const ldso_ba_ctx *c, const float *dev_order, float *out) {
+    long long out_base = 0;
+    for (int w = 0; w < c->n_win; w++) {
+        const WinDev &D = c->wd[w];
+        const WinHost &H = c->wh[w];
+        for (int q = 0; q < D.P; q++) out[out_base + H.pt_orig[q]] = dev_order[D.point_base + q];
+        out_base += H.P_all;
+    }
 }
 ResubParams resub_params(ldso_ba_ctx *c, int begin, int count, double lambda, bool apply_step) {
     ResubParams R{};
@@ -4733,17 +4762,13 @@ size_t stitch_host_smem_bytes(int N, int *th_cap) {
 
 }  // namespace
 
-namespace {
-void shard_points(const ldso_ba_window &in, int rank, int count, std::vector<int> &out);
-}  // namespace
-
 // =========================================================================================
 // C ABI
 // =========================================================================================
 extern "C" {
 
 int ldso_ba_abi_version(void) { return LDSO_BA_ABI_VERSION; }
-const char *ldso_ba_last_error(void) { return g_err.c_str(); }
+const char *ldso_ba_last_error(void) { return last_error(); }
 
 int ldso_ba_frame_precalc(int32_t n, const ldso_ba_frame_state *f, const float calib[4], float *out) {
     if (n < 1 || n > LDSO_BA_MAX_FRAMES || !f || !calib || !out) return fail(-1, "bad arguments");
@@ -4914,70 +4939,7 @@ void ldso_ba_destroy(ldso_ba_ctx *c) {
     if (c->pin_map) (void)hipHostFree(c->pin_map);
     if (c->pin_in) (void)hipHostFree(c->pin_in);
     if (c->pin_in_ev) (void)hipEventDestroy(c->pin_in_ev);
-    c->d_wins.release();
-    c->d_img.release();
-    c->d_act_in.release();
-    c->d_act_out.release();
-    c->d_precalc.release();
-    c->d_frame_th.release();
-    c->d_pt_data.release();
-    c->d_pt_out.release();
-    c->d_pt_step.release();
-    c->d_adH.release();
-    c->d_adT.release();
-    c->d_rs_slot.release();
-    c->d_pt_nres.release();
-    c->d_pt_tgt.release();
-    c->d_pair_win.release();
-    c->d_frame_win.release();
-    c->d_pt_host.release();
-    c->d_rs_tgt.release();
-    c->d_rs_flags.release();
-    c->d_rs_state.release();
-    c->d_rs_newstate.release();
-    c->d_rs_energy.release();
-    c->d_rs_newenergy.release();
-    c->d_rs_energy_wo.release();
-    c->d_rs_center.release();
-    c->d_rec_a.release();
-    c->d_rec_b.release();
-    c->d_geo_snap.release();
-    c->d_top_items.release();
-    c->d_sc_items.release();
-    c->d_adhtd.release();
-    c->d_pair_items.release();
-    c->d_host_items.release();
-    c->d_top_slab.release();
-    c->d_sc_slab.release();
-    c->d_item_energy.release();
-    c->d_sys.release();
-    c->d_stage.release();
-    c->d_sum_blocks.release();
-    c->d_x_local.release();
-    c->d_x_gathered.release();
-    c->d_fstate.release();
-    c->d_calib_val.release();
-    c->d_calib_zero.release();
-    c->d_cprior.release();
-    c->d_ehist.release();
-    c->d_stop.release();
-    c->d_status.release();
-    c->d_add_priors.release();
     if (c->comm) (void)ncclCommDestroy(c->comm);
-    c->d_xad.release();
-    c->d_sx_state.release();
-    c->d_sx_newstate.release();
-    c->d_sx_flags.release();
-    c->d_sx_energy.release();
-    c->d_sx_newenergy.release();
-    c->d_sx_ewo.release();
-    c->d_sx_center.release();
-    c->d_sx_rec_a.release();
-    c->d_sx_rec_b.release();
-    c->d_sx_geo_snap.release();
-    c->d_jp_out.release();
-    c->d_pt_vals.release();
-    c->d_sx_item.release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -4987,32 +4949,29 @@ void *ldso_ba_stream(ldso_ba_ctx *c) { return c ? (void *)c->stream : nullptr; }
 }  // extern "C"
 
 namespace {
-// SURVEY.md §8e's partition: points in host-frame order, cut into shard_count contiguous runs of
-// (as nearly as possible) equal residual counts, so a shard holds whole host frames except at
-// its two ends (a host is split only where a cut falls inside it, e.g. when shards outnumber
-// hosts).  Rank r owns the points whose first residual lies in [r T / G, (r + 1) T / G).
-void shard_points(const ldso_ba_window &in, int rank, int count, std::vector<int> &out) {
-    out.clear();
-    // the device point order: host frames in window order, each host's points in features order
-    // (point_rank; the caller's order without it)
-    std::vector<int> order;
-    order.reserve(in.n_points);
-    for (int f = 0; f < in.n_frames; f++) {
-        const size_t b = order.size();
-        for (int p = 0; p < in.n_points; p++)
-            if (in.point_host[p] == f) order.push_back(p);
-        if (in.point_rank)
-            std::stable_sort(order.begin() + b, order.end(),
-                             [&](int a, int c) { return in.point_rank[a] < in.point_rank[c]; });
+// The device buffers of one load, allocated in call order (never fewer than one element, so every
+// pointer is valid); host arrays given with put() are uploaded by upload() once all are allocated.
+// The first failed allocation ends the list: later calls do nothing and rc keeps its code.
+struct LoadList {
+    ldso_ba_ctx *c;
+    int rc = 0;
+    std::vector<InBatch::Item> ups;
+    template <typename T>
+    void alloc(DevBuf<T> &buf, size_t count) {
+        if (!rc) rc = buf.alloc(std::max<size_t>(1, count));
     }
-    const long long T = in.n_residuals;
-    long long acc = 0;
-    for (int p : order) {
-        const long long owner = T > 0 ? std::min<long long>(count - 1, acc * count / T) : p % count;
-        if (owner == rank) out.push_back(p);
-        acc += in.point_res_begin[p + 1] - in.point_res_begin[p];
+    template <typename T, typename V>
+    void put(DevBuf<T> &buf, const std::vector<V> &v) {
+        static_assert(sizeof(T) == sizeof(V), "uploaded as is");
+        alloc(buf, v.size());
+        if (!rc) ups.push_back({buf.p, v.data(), v.size() * sizeof(V)});
     }
-}
+    int upload() {
+        for (const InBatch::Item &u : ups)
+            if (!rc && u.bytes) HIP_TRY(hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
+        return rc;
+    }
+};
 
 // parent != nullptr: a marginalisation context over `ws[0]` whose frames are the parent's window
 // parent_win (images borrowed, not uploaded; priorF scaled by setting_idepthFixPriorMargFac)
@@ -5021,12 +4980,9 @@ int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32
     if (!c || n_windows < 1 || !ws) return fail(-1, "bad arguments");
     if (shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return fail(-1, "bad shard");
     c->th_host_valid = false;
-    for (int w = 0; w < n_windows; w++) {
-        int rc = check_window(ws[w], parent == nullptr);
-        if (rc) return rc;
-        if (ws[w].width != ws[0].width || ws[w].height != ws[0].height)
-            return fail(-1, "all windows of a context must share the image size");
-    }
+    Layout L;
+    int rc = build_layout(ws, n_windows, shard_rank, shard_count, c->item_order, c->top_chunk, parent != nullptr, L);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->n_win = n_windows;
@@ -5046,360 +5002,76 @@ int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32
     } else {
         image_geometry(c);
     }
-    c->wh.assign(n_windows, WinHost());
+    c->wh = std::move(L.wh);
     c->wd.assign(n_windows, WinDev());
+    // WinDev is WinDesc under the name the kernels' symbols carry (see WinDev): keep both, copy across
+    for (int w = 0; w < n_windows; w++) static_cast<WinDesc &>(c->wd[w]) = L.wd[w];
     c->sys_host_valid = false;
     c->energy_valid = false;
-
-    // host-side layout
-    std::vector<int4> top_items, sc_items;
-    std::vector<int2> pair_items, host_items;
-    std::vector<int> pair_win, frame_win, rs_slot, pt_nres, pt_host;
-    std::vector<unsigned long long> pt_tgt;
-    int rec_base = 0;
-    std::vector<uint8_t> rs_tgt, rs_flags;
-    std::vector<int8_t> rs_state;
-    std::vector<float> rs_energy, pt_data, precalc, frame_th;
-    std::vector<double> adH, adT;
-    long long sc_slab_total = 0, sys_total = 0, stage_total = 0;
-    int vec_total = 0;
-    std::vector<int> pt_win;
-    // residuals per k_linearize wave: 64 when the grid is large anyway; small workloads (one
-    // window) use shorter chunks so more waves start at once (latency, not throughput, bound)
-    long long r_est = 0;
-    for (int w = 0; w < n_windows; w++) r_est += ws[w].n_residuals;
-    r_est /= shard_count;
-    const int chunk = c->top_chunk ? c->top_chunk : r_est >= 64LL * 4096 ? 64 : r_est >= 32LL * 2048 ? 32 : 16;
-    // k_point_sc points per block: 64 for large loads; a small load (one window: 32 blocks of 64
-    // points on 256 CUs) takes 16-point blocks, whose SYRK chains are a quarter as long (one S7
-    // window's pass 30 -> 28 us; optimize unchanged: its sumNID block is the longest there)
-    const int sc_chunk = r_est < 64LL * 4096 ? 16 : kScPoints;
-    int frame_base = 0, pair_base = 0, point_base = 0, res_base = 0;
-    size_t smem_max = 0;
-
-    for (int w = 0; w < n_windows; w++) {
-        const ldso_ba_window &in = ws[w];
-        WinHost &H = c->wh[w];
-        WinDev &D = c->wd[w];
-        const int N = in.n_frames;
-        H.N = N;
-        H.P_all = in.n_points;
-        H.R_all = in.n_residuals;
-        // the priors (HL, bL) are not part of the reduced packed system: every rank adds them in
-        // its own (redundant) solve, so every shard keeps them
-        H.add_priors = true;
-        H.c_prior.assign(in.c_prior, in.c_prior + 4);
-        H.c_delta.assign(in.c_delta, in.c_delta + 4);
-        H.frame_prior.assign(in.frame_prior, in.frame_prior + 8 * N);
-        H.frame_delta_prior.assign(in.frame_delta_prior, in.frame_delta_prior + 8 * N);
-        H.adHF.resize((size_t)N * N * 64);
-        H.adTF.resize((size_t)N * N * 64);
-        for (size_t k = 0; k < H.adHF.size(); k++) {
-            H.adHF[k] = (float)in.ad_host[k];
-            H.adTF[k] = (float)in.ad_target[k];
-        }
-        // points of this shard (host-frame partition, shard_points)
-        shard_points(in, shard_rank, shard_count, H.pt_orig);
-        const int P = (int)H.pt_orig.size();
-        H.P = P;
-        // residual bucket sort by pair index h + N t (stable in point order)
-        std::vector<int> bucket_cnt(N * N, 0);
-        int R = 0;
-        for (int q = 0; q < P; q++) {
-            const int p = H.pt_orig[q], h = in.point_host[p];
-            for (int k = in.point_res_begin[p]; k < in.point_res_begin[p + 1]; k++) {
-                bucket_cnt[h + N * in.res_target[k]]++;
-                R++;
-            }
-        }
-        H.R = R;
-        std::vector<int> bucket_start(N * N + 1, 0);
-        for (int b = 0; b < N * N; b++) bucket_start[b + 1] = bucket_start[b] + bucket_cnt[b];
-        std::vector<int> fill(bucket_start.begin(), bucket_start.end() - 1);
-        H.rs_orig.assign(R, -1);
-        std::vector<int> res_pos_of(in.n_residuals, -1);
-        for (int q = 0; q < P; q++) {
-            const int p = H.pt_orig[q], h = in.point_host[p];
-            for (int k = in.point_res_begin[p]; k < in.point_res_begin[p + 1]; k++) {
-                const int pos = fill[h + N * in.res_target[k]]++;
-                H.rs_orig[pos] = k;
-                res_pos_of[k] = pos;
-            }
-        }
-        // item order 2: inside each bucket the residuals are ranked by their projection into the
-        // target (row, then column) and dealt round robin, in groups of 8 consecutive ranks (one
-        // phase-A step of a wavefront), over the bucket's chunks: every chunk of a bucket sweeps the
-        // target image top to bottom and the concurrent chunks of one target are at the same band
-        // at the same step (the target's live lines: one band, not the frame).  Chunks stay
-        // multiples of 8 but the last, so the phase-A steps are the same as in order 0.
-        std::vector<int> bucket_nch(N * N, 0);
-        std::vector<int> chunk_len;  // item order 2: residuals per chunk, bucket by bucket
-        if (c->item_order == 2) {
-            std::vector<std::pair<std::pair<float, float>, int>> key;
-            for (int b = 0; b < N * N; b++) {
-                const int n = bucket_cnt[b];
-                if (n == 0) continue;
-                const float *pre = in.precalc + (size_t)b * LDSO_BA_PRECALC_STRIDE;  // PRE_KRKiTll, PRE_KtTll
-                key.clear();
-                for (int pos = bucket_start[b]; pos < bucket_start[b + 1]; pos++) key.push_back({{0.f, 0.f}, H.rs_orig[pos]});
-                for (auto &e : key) {
-                    const int k = e.second;  // its point: point_res_begin is sorted
-                    const int p = (int)(std::upper_bound(in.point_res_begin, in.point_res_begin + in.n_points + 1, k) -
-                                        in.point_res_begin) - 1;
-                    const float *d = in.point_data + (size_t)p * LDSO_BA_POINT_STRIDE;
-                    float q[3];
-                    for (int i = 0; i < 3; i++) q[i] = pre[3 * i] * d[0] + pre[3 * i + 1] * d[1] + pre[3 * i + 2] + pre[9 + i] * d[2];
-                    const float y = q[1] / q[2], x = q[0] / q[2];
-                    e.first = {std::isfinite(y) ? y : 0.f, std::isfinite(x) ? x : 0.f};
-                }
-                std::sort(key.begin(), key.end());
-                const int G = (n + 7) / 8, nch = (n + chunk - 1) / chunk;
-                bucket_nch[b] = nch;
-                std::vector<int> start(nch + 1, 0);
-                for (int cc = 0; cc < nch; cc++) {
-                    const int groups = (G - cc + nch - 1) / nch;  // groups cc, cc + nch, ...
-                    int len = 8 * groups;
-                    if ((G - 1) % nch == cc) len -= 8 * G - n;  // the last (short) group ends this chunk
-                    start[cc + 1] = start[cc] + len;
-                    chunk_len.push_back(len);
-                }
-                for (int i = 0; i < n; i++) {
-                    const int g = i / 8, cc = g % nch;
-                    const int pos = bucket_start[b] + start[cc] + 8 * (g / nch) + (i & 7);
-                    H.rs_orig[pos] = key[i].second;
-                    res_pos_of[key[i].second] = pos;
-                }
-            }
-        }
-        // per-residual arrays (global, sorted)
-        for (int pos = 0; pos < R; pos++) {
-            const int k = H.rs_orig[pos];
-            rs_tgt.push_back((uint8_t)in.res_target[k]);
-            rs_flags.push_back(in.res_flags[k]);
-            rs_state.push_back(in.res_state[k]);
-            rs_energy.push_back(in.res_energy[k]);
-            rs_slot.push_back(0);
-        }
-        H.rs_slot.assign(R, 0);
-        // per-point arrays
-        H.pt_host.resize(P);
-        for (int q = 0; q < P; q++) {
-            const int p = H.pt_orig[q];
-            H.pt_host[q] = in.point_host[p];
-            pt_host.push_back(in.point_host[p]);
-            pt_data.insert(pt_data.end(), in.point_data + (size_t)p * LDSO_BA_POINT_STRIDE,
-                           in.point_data + (size_t)(p + 1) * LDSO_BA_POINT_STRIDE);
-            if (c->marg)  // marginalizePointsF: p->priorF *= setting_idepthFixPriorMargFac (EnergyFunctional.cc:216)
-                pt_data[pt_data.size() - LDSO_BA_POINT_STRIDE + 4] *= kIdepthFixPriorMargFac;
-            const int b = in.point_res_begin[p], e = in.point_res_begin[p + 1];
-            pt_nres.push_back(e - b);
-            unsigned long long tg = 0;
-            for (int k = 0; k < e - b; k++) {
-                const int pos = res_pos_of[b + k];
-                const int tgk = in.res_target[b + k], hk = in.point_host[p];
-                const int slot = rec_base + (tgk < hk ? tgk : tgk - 1) * P + q;
-                rs_slot[res_base + pos] = slot;
-                H.rs_slot[pos] = slot;
-                tg |= (unsigned long long)in.res_target[b + k] << (4 * k);
-            }
-            pt_tgt.push_back(tg);
-        }
-        // descriptors
-        D.N = N;
-        D.P = P;
-        D.R = R;
-        D.D = 8 * N + 4;
-        D.frame_base = frame_base;
-        D.pair_base = pair_base;
-        D.point_base = point_base;
-        D.res_base = res_base;
-        D.width = in.width;
-        D.height = in.height;
-        D.wM3 = (float)(in.width - 3);
-        D.hM3 = (float)(in.height - 3);
-        for (int i = 0; i < 4; i++) D.calib[i] = in.calib[i];
-        for (int i = 0; i < 4; i++) D.cdelta[i] = in.c_delta[i];
-        D.p_all = in.n_points;  // numID counts every shard's points
-        D.K = 8 * (N - 1) + 5;
-        D.KP = (D.K + 3) / 4 * 4;
-        const int nt = D.KP / 4;
-        D.ntiles = nt * (nt + 1) / 2;
-        smem_max = std::max(smem_max, sc_smem_bytes(D.KP));
-        // top items: chunks of `chunk` residuals of one bucket (one wave each)
-        D.top_item_base = (int)top_items.size();
-        const size_t pi0 = pair_items.size();
-        pair_items.resize(pi0 + (size_t)N * N);
-        std::vector<int> chunk_off(N * N + 1, 0);  // item order 2: first chunk_len entry of each bucket
-        for (int b = 0; b < N * N; b++) chunk_off[b + 1] = chunk_off[b] + bucket_nch[b];
-        for (int bb = 0; bb < N * N; bb++) {
-            // bucket b = h + N t; chunks in target-major order (the N-1 buckets reading one target
-            // image run together) or host-major (the buckets of one host's points run together)
-            const int b = c->item_order == 1 ? (bb / N) + N * (bb % N) : bb;
-            const int first = (int)top_items.size();
-            if (bucket_nch[b] > 0) {  // item order 2: the chunks dealt above
-                int s0 = bucket_start[b];
-                for (int cc = 0; cc < bucket_nch[b]; cc++) {
-                    const int len = chunk_len[chunk_off[b] + cc];
-                    top_items.push_back(make_int4(res_base + s0, len | (cc == 0 ? 1 << 16 : 0), pair_base + b, w));
-                    s0 += len;
-                }
-            } else {
-                for (int s = bucket_start[b]; s < bucket_start[b + 1]; s += chunk)  // bit 16: the pair's first chunk
-                    top_items.push_back(make_int4(res_base + s, std::min(chunk, bucket_start[b + 1] - s) | (s == bucket_start[b] ? 1 << 16 : 0),
-                                                  pair_base + b, w));
-            }
-            pair_items[pi0 + b] = make_int2(first, (int)top_items.size() - first);
-        }
-        for (int b = 0; b < N * N; b++) pair_win.push_back(w);
-        D.n_top_items = (int)top_items.size() - D.top_item_base;
-        // sc items: chunks of kScPoints points of one host
-        D.sc_item_base = (int)sc_items.size();
-        {
-            int q = 0;
-            for (int f = 0; f < N; f++) {
-                const int first = (int)sc_items.size();
-                int q0 = q;
-                while (q < P && H.pt_host[q] == f) q++;
-                for (int s = q0; s < q; s += sc_chunk)
-                    sc_items.push_back(make_int4(point_base + s, std::min(sc_chunk, q - s), f, w));
-                host_items.push_back(make_int2(first, (int)sc_items.size() - first));
-                frame_win.push_back(w);
-            }
-        }
-        D.n_sc_items = (int)sc_items.size() - D.sc_item_base;
-        D.sc_slab_base = sc_slab_total;
-        sc_slab_total += (long long)D.n_sc_items * D.ntiles * 16;
-        D.sys_base = sys_total;
-        sys_total += sys_len(D.D);
-        D.stage_base = stage_total;
-        // k_stitch's per-pair records, or k_stitch_host's per-host partial systems
-        stage_total += std::max<long long>((long long)N * N * stage_rec(N), (long long)N * sys_len(D.D));
-        D.newest_begin = res_base + bucket_start[N * (N - 1)];
-        D.newest_end = res_base + bucket_start[N * N];
-        D.rec_base = rec_base;
-        D.vec_base = vec_total;
-        vec_total += D.D;
-        pt_win.insert(pt_win.end(), P, w);
-        // frame-level inputs
-        precalc.insert(precalc.end(), in.precalc, in.precalc + (size_t)N * N * LDSO_BA_PRECALC_STRIDE);
-        adH.insert(adH.end(), in.ad_host, in.ad_host + (size_t)N * N * 64);
-        adT.insert(adT.end(), in.ad_target, in.ad_target + (size_t)N * N * 64);
-        frame_th.insert(frame_th.end(), in.frame_energy_th, in.frame_energy_th + N);
-        frame_base += N;
-        pair_base += N * N;
-        point_base += P;
-        rec_base += P * (N - 1);
-        res_base += R;
-    }
-    c->n_top_items = (int)top_items.size();
-    c->n_sc_items = (int)sc_items.size();
-    c->n_pairs = pair_base;
-    c->n_frames = frame_base;
-    c->max_frames = 0;
-    for (int w = 0; w < n_windows; w++) c->max_frames = std::max(c->max_frames, ws[w].n_frames);
-    c->host_stitch = c->max_frames <= kHostStitchMaxN && !getenv_flag("LDSO_BA_STITCH_RECORDS");
-    c->P_tot = point_base;
-    c->vec_total = vec_total;
-    c->R_tot = res_base;
-    c->sc_smem_max = smem_max;
-
-    int rc = 0;
-#define ALLOC(buf, n)                   \
-    do {                                \
-        rc = (buf).alloc(n);            \
-        if (rc) return rc;              \
-    } while (0)
-    ALLOC(c->d_wins, n_windows);
-    if (c->marg) c->d_img.release();
-    else ALLOC(c->d_img, (size_t)c->n_frames * c->frame_stride);
-    if (c->marg) ALLOC(c->d_adhtd, (size_t)c->n_pairs * 8);
-    ALLOC(c->d_precalc, precalc.size());
-    ALLOC(c->d_frame_th, frame_th.size());
-    ALLOC(c->d_pt_data, std::max<size_t>(1, pt_data.size()));
-    ALLOC(c->d_pt_out, std::max<size_t>(1, (size_t)c->P_tot * 12));
-    ALLOC(c->d_pt_step, std::max<size_t>(1, (size_t)c->P_tot));
-    ALLOC(c->d_pt_host, std::max<size_t>(1, pt_host.size()));
-    ALLOC(c->d_adH, adH.size());
-    ALLOC(c->d_adT, adT.size());
-    ALLOC(c->d_pt_nres, std::max<size_t>(1, pt_nres.size()));
-    ALLOC(c->d_rs_slot, std::max<size_t>(1, rs_slot.size()));
-    ALLOC(c->d_pt_tgt, std::max<size_t>(1, pt_tgt.size()));
-    ALLOC(c->d_pair_win, pair_win.size());
-    ALLOC(c->d_frame_win, frame_win.size());
-    ALLOC(c->d_rs_tgt, std::max<size_t>(1, rs_tgt.size()));
-    ALLOC(c->d_rs_flags, std::max<size_t>(1, rs_flags.size()));
-    ALLOC(c->d_rs_state, std::max<size_t>(1, rs_state.size()));
-    ALLOC(c->d_rs_newstate, std::max<size_t>(1, rs_state.size()));
-    ALLOC(c->d_rs_energy, std::max<size_t>(1, rs_energy.size()));
-    ALLOC(c->d_rs_newenergy, std::max<size_t>(1, rs_energy.size()));
-    ALLOC(c->d_rs_energy_wo, std::max<size_t>(1, rs_energy.size()));
-    ALLOC(c->d_rs_center, std::max<size_t>(1, rs_energy.size()));
-    ALLOC(c->d_rec_a, std::max<size_t>(1, (size_t)rec_base));
-    ALLOC(c->d_rec_b, std::max<size_t>(1, (size_t)rec_base));
-    ALLOC(c->d_geo_snap, std::max<size_t>(1, (size_t)pair_base * kGeoSnap));
-    ALLOC(c->d_top_items, std::max<size_t>(1, top_items.size()));
-    ALLOC(c->d_sc_items, std::max<size_t>(1, sc_items.size()));
-    ALLOC(c->d_pair_items, pair_items.size());
-    ALLOC(c->d_host_items, host_items.size());
-    ALLOC(c->d_top_slab, std::max<size_t>(1, top_items.size() * kTopVals));
-    ALLOC(c->d_sc_slab, std::max<size_t>(1, (size_t)sc_slab_total));
-    ALLOC(c->d_item_energy, std::max<size_t>(1, top_items.size() * 2));
-    ALLOC(c->d_sys, (size_t)sys_total + 4 * (size_t)n_windows);  // + win_energy() + win_nid()
-    c->sys_n = (size_t)sys_total;
-    ALLOC(c->d_stage, (size_t)std::max<long long>(1, stage_total));
-    {
-        std::vector<int2> sb;
-        for (int w = 0; w < n_windows; w++) {
-            const long long n_el = sys_len(c->wd[w].D);
-            for (long long e0 = 0; e0 < n_el; e0 += 256) sb.push_back(make_int2(w, (int)e0));
-        }
-        c->n_sum_blocks = (int)sb.size();
-        ALLOC(c->d_sum_blocks, sb.size());
-        HIP_TRY(hipMemcpyAsync(c->d_sum_blocks.p, sb.data(), sb.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
-    }
-    ALLOC(c->d_xad, (size_t)n_windows * kXadStride);
-    ALLOC(c->d_prior, (size_t)2 * vec_total);
-    ALLOC(c->d_x, (size_t)vec_total);
-    ALLOC(c->d_ns, (size_t)7 * vec_total);
-    ALLOC(c->d_ns_nm, (size_t)7 * vec_total);
-    ALLOC(c->d_ns_g, (size_t)kPrepGStride * n_windows);
+    c->n_top_items = (int)L.top_items.size();
+    c->n_sc_items = (int)L.sc_items.size();
+    c->n_pairs = (int)L.pair_win.size();
+    c->n_frames = (int)L.frame_win.size();
+    c->max_frames = L.max_frames;
+    c->host_stitch = c->max_frames <= kHostStitchMaxN && !read_switches().stitch_records;
+    c->P_tot = (int)L.pt_host.size();
+    c->vec_total = L.vec_total;
+    c->R_tot = (int)L.rs_tgt.size();
+    c->sc_smem_max = L.smem_max;
+    c->sys_n = (size_t)L.sys_total;
+    c->n_sum_blocks = (int)L.sum_blocks.size();
     c->ns_cache.clear();
     c->ns_cache_null = -1;
-    ALLOC(c->d_pt_win, std::max<size_t>(1, pt_win.size()));
-#undef ALLOC
-    auto up = [&](void *dst, const void *src, size_t bytes) -> int {
-        if (bytes == 0) return 0;
-        HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-        return 0;
-    };
-#define UP(buf, vec)                                                   \
-    do {                                                               \
-        rc = up((buf).p, (vec).data(), (vec).size() * sizeof((vec)[0])); \
-        if (rc) return rc;                                             \
-    } while (0)
-    UP(c->d_wins, c->wd);
-    UP(c->d_precalc, precalc);
-    UP(c->d_frame_th, frame_th);
-    UP(c->d_pt_data, pt_data);
-    UP(c->d_pt_host, pt_host);
-    UP(c->d_adH, adH);
-    UP(c->d_adT, adT);
-    UP(c->d_pt_nres, pt_nres);
-    UP(c->d_rs_slot, rs_slot);
-    UP(c->d_pt_tgt, pt_tgt);
-    UP(c->d_pt_win, pt_win);
-    UP(c->d_pair_win, pair_win);
-    UP(c->d_frame_win, frame_win);
-    UP(c->d_rs_tgt, rs_tgt);
-    UP(c->d_rs_flags, rs_flags);
-    UP(c->d_rs_state, rs_state);
-    UP(c->d_rs_energy, rs_energy);
-    UP(c->d_rs_newenergy, rs_energy);
-    UP(c->d_top_items, top_items);
-    UP(c->d_sc_items, sc_items);
-    UP(c->d_pair_items, pair_items);
-    UP(c->d_host_items, host_items);
-#undef UP
+
+    const size_t P = (size_t)c->P_tot, R = (size_t)c->R_tot, nw = (size_t)n_windows, vt = (size_t)L.vec_total;
+    const std::vector<float> neg(R, -1.0f);  // rs_energy_wo: nothing evaluated yet
+    LoadList A{c};
+    A.put(c->d_wins, L.wd);
+    if (c->marg) c->d_img.release();
+    else A.alloc(c->d_img, (size_t)c->n_frames * c->frame_stride);
+    if (c->marg) A.alloc(c->d_adhtd, (size_t)c->n_pairs * 8);
+    A.put(c->d_precalc, L.precalc);
+    A.put(c->d_frame_th, L.frame_th);
+    A.put(c->d_pt_data, L.pt_data);
+    A.alloc(c->d_pt_out, P * 12);
+    A.alloc(c->d_pt_step, P);
+    A.put(c->d_pt_host, L.pt_host);
+    A.put(c->d_adH, L.adH);
+    A.put(c->d_adT, L.adT);
+    A.put(c->d_pt_nres, L.pt_nres);
+    A.put(c->d_rs_slot, L.rs_slot);
+    A.put(c->d_pt_tgt, L.pt_tgt);
+    A.put(c->d_pair_win, L.pair_win);
+    A.put(c->d_frame_win, L.frame_win);
+    A.put(c->d_rs_tgt, L.rs_tgt);
+    A.put(c->d_rs_flags, L.rs_flags);
+    A.put(c->d_rs_state, L.rs_state);
+    A.alloc(c->d_rs_newstate, R);
+    A.put(c->d_rs_energy, L.rs_energy);
+    A.put(c->d_rs_newenergy, L.rs_energy);
+    A.put(c->d_rs_energy_wo, neg);
+    A.alloc(c->d_rs_center, R);
+    A.alloc(c->d_rec_a, (size_t)L.rec_base);
+    A.alloc(c->d_rec_b, (size_t)L.rec_base);
+    A.alloc(c->d_geo_snap, (size_t)c->n_pairs * kGeoSnap);
+    A.put(c->d_top_items, L.top_items);
+    A.put(c->d_sc_items, L.sc_items);
+    A.put(c->d_pair_items, L.pair_items);
+    A.put(c->d_host_items, L.host_items);
+    A.alloc(c->d_top_slab, L.top_items.size() * kTopVals);
+    A.alloc(c->d_sc_slab, (size_t)L.sc_slab_total);
+    A.alloc(c->d_item_energy, L.top_items.size() * 2);
+    A.alloc(c->d_sys, c->sys_n + 4 * nw);  // + win_energy() + win_nid()
+    A.alloc(c->d_stage, (size_t)L.stage_total);
+    A.put(c->d_sum_blocks, L.sum_blocks);
+    A.alloc(c->d_xad, nw * kXadStride);
+    A.alloc(c->d_prior, 2 * vt);
+    A.alloc(c->d_x, vt);
+    A.alloc(c->d_ns, 7 * vt);
+    A.alloc(c->d_ns_nm, 7 * vt);
+    A.alloc(c->d_ns_g, (size_t)kPrepGStride * nw);
+    A.put(c->d_pt_win, L.pt_win);
+    if ((rc = A.upload())) return rc;
     HIP_TRY(hipMemsetAsync(c->d_rs_center.p, 0, c->d_rs_center.bytes(), c->stream));
     HIP_TRY(hipMemsetAsync(c->d_rec_a.p, 0, c->d_rec_a.bytes(), c->stream));
     HIP_TRY(hipMemsetAsync(c->d_rec_b.p, 0xFF, c->d_rec_b.bytes(), c->stream));  // NaN: not active
@@ -5408,12 +5080,7 @@ int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32
     HIP_TRY(hipMemsetAsync(c->d_pt_step.p, 0, c->d_pt_step.bytes(), c->stream));
     HIP_TRY(hipMemsetAsync(c->d_sys.p, 0, c->d_sys.bytes(), c->stream));
     HIP_TRY(hipMemsetAsync(c->d_rs_newstate.p, LDSO_BA_RES_OUTLIER, c->d_rs_newstate.bytes(), c->stream));
-    {
-        std::vector<float> neg(rs_energy.size(), -1.0f);
-        rc = up(c->d_rs_energy_wo.p, neg.data(), neg.size() * sizeof(float));
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
     // images: per frame through a float3 staging buffer, repacked on the device; the
     // intensity-only layout falls back to 2x4 float4 tiles if the caller's gradients are not
     // makeImages' (then recomputing them would not be exact)
@@ -5588,7 +5255,7 @@ namespace {
 // after which k_frame_th re-selects the exact setNewFrameEnergyTH threshold on every rank, and,
 // inside ldso_ba_optimize, the rank's run of |idepth|, from which every rank walks the window's
 // whole sumNID chain (doStepFromBackup's float sum in the unsharded order: nid_source).
-int comm_exchange(ldso_ba_ctx *c, bool accumulate) {
+int comm_exchange(ldso_ba_ctx *c, bool accumulate, const Switches &sw) {
     hipStream_t st = c->stream;
     if (c->x_stride == 0) {  // first exchange since the load: agree on the slot stride and run length
         int64_t m[2] = {1, 0};
@@ -5623,7 +5290,7 @@ int comm_exchange(ldso_ba_ctx *c, bool accumulate) {
     HIP_TRY(hipGetLastError());
     NCCL_TRY(ncclAllGather(c->d_x_local.p, c->d_x_gathered.p, (size_t)c->n_win * slot, ncclFloat32, c->comm, st));
     // the chains run here when the solve does not host them (exact solve modes)
-    const bool chain_here = nid && !nid_in_solve(c);
+    const bool chain_here = nid && !nid_in_solve(c, sw);
     NidSrc src = chain_here ? nid_source(c) : NidSrc{};
     const int* stop = c->opt_pass >= 0 ? c->d_stop.p : nullptr;
     return timed_launch(c, 4, st, [&] {
@@ -5659,7 +5326,8 @@ int ldso_ba_comm_init(ldso_ba_ctx *c, const uint8_t *id_in, int32_t rank, int32_
     return 0;
 }
 
-int ldso_ba_linearize(ldso_ba_ctx *c, int32_t fix, int32_t accumulate) {
+// ldso_ba_linearize under the caller's reading of the switches
+static int linearize_pass(ldso_ba_ctx *c, int fix, int accumulate, const Switches &sw) {
     if (!c || c->n_win == 0) return fail(-1, "no windows loaded");
     int rc;
     if ((rc = ldso_ba_check_settings(&c->settings))) return rc;
@@ -5667,98 +5335,35 @@ int ldso_ba_linearize(ldso_ba_ctx *c, int32_t fix, int32_t accumulate) {
     c->sys_host_valid = false;
     c->energy_valid = false;
     c->th_host_valid = false;
-    LinParams L{};
-    L.items = c->d_top_items.p;
-    L.wins = c->d_wins.p;
-    L.img = c->img_ext ? c->img_ext : c->d_img.p;
-    L.ad_ht_delta = c->marg ? c->d_adhtd.p : nullptr;
-    L.precalc = c->d_precalc.p;
-    L.frame_th = c->d_frame_th.p;
-    L.rs_slot = c->d_rs_slot.p;
-    L.pt_data = c->d_pt_data.p;
-    L.rs_state = c->d_rs_state.p;
-    L.rs_newstate = c->d_rs_newstate.p;
-    L.rs_flags = c->d_rs_flags.p;
-    L.rs_energy = c->d_rs_energy.p;
-    L.rs_newenergy = c->d_rs_newenergy.p;
-    L.rs_energy_wo = c->d_rs_energy_wo.p;
-    L.rs_center = reinterpret_cast<float *>(c->d_rs_center.p);
-    L.center_stride = c->R_tot;
-    L.rec_a = c->d_rec_a.p;
-    L.rec_b = c->d_rec_b.p;
-    L.geo_snap = c->d_geo_snap.p;
-    L.top_slab = c->d_top_slab.p;
-    L.item_energy = c->d_item_energy.p;
-    L.frame_stride = c->frame_stride;
-    L.tiles_per_row = c->tiles_per_row;
+    const bool in_opt = c->opt_pass >= 0;
+    LinParams L = lin_params(c);
     L.fix = fix;
     L.accumulate = accumulate;
-    L.aff_fix = aff_fix_bits(c);
-    L.item_base = 0;
-    L.n_items = c->n_top_items;
-    L.n_blocks = (L.n_items + 3) / 4;
-    PointParams Pp{};
-    Pp.items = c->d_sc_items.p;
-    Pp.wins = c->d_wins.p;
-    Pp.pt_data = c->d_pt_data.p;
-    Pp.pt_nres = c->d_pt_nres.p;
-    Pp.pt_tgt = c->d_pt_tgt.p;
-    Pp.rec_a = c->d_rec_a.p;
-    Pp.rec_b = c->d_rec_b.p;
-    Pp.precalc = c->d_precalc.p;
-    Pp.pt_out = c->d_pt_out.p;
-    Pp.sc_slab = c->d_sc_slab.p;
-    Pp.shift_prior = c->marg ? 0 : 1;
-    Pp.item_base = 0;
-    Pp.n_items = c->n_sc_items;
-    StitchParams Sp{};
-    Sp.wins = c->d_wins.p;
-    Sp.pair_win = c->d_pair_win.p;
-    Sp.e_wo = c->d_rs_energy_wo.p;
-    Sp.frame_th = c->d_frame_th.p;
-    Sp.pair_items = c->d_pair_items.p;
-    Sp.top_slab = c->d_top_slab.p;
-    Sp.item_energy = c->d_item_energy.p;
-    Sp.host_items = c->d_host_items.p;
-    Sp.sc_slab = c->d_sc_slab.p;
-    Sp.adH = c->d_adH.p;
-    Sp.adT = c->d_adT.p;
-    Sp.sys = c->d_sys.p;
-    Sp.stage = c->d_stage.p;
-    Sp.win_energy = c->win_energy();
-    const bool in_opt = c->opt_pass >= 0;
+    PointParams Pp = point_params(c);
+    StitchParams Sp = stitch_params(c);
     Sp.ehist = in_opt && !c->comm ? c->d_ehist.p : nullptr;  // with RCCL: after the exchange
-    Sp.pass = c->opt_pass;
-    Sp.stop = in_opt ? c->d_stop.p : nullptr;
-    L.stop = Sp.stop;
-    L.pass = c->opt_pass;
-    Pp.stop = Sp.stop;
-    Pp.pass = c->opt_pass;
+    Sp.accumulate = accumulate;
+    L.stop = Pp.stop = Sp.stop = in_opt ? c->d_stop.p : nullptr;
+    L.pass = Pp.pass = Sp.pass = c->opt_pass;
     const size_t sc_smem = std::max<size_t>(c->sc_smem_max, 4096);  // point_nid stages >= 1024 idepths
-    if (in_opt && accumulate && !nid_in_solve(c) && !c->comm) {  // the next step's sumNID / numID (its backup idepths are this pass's)
+    if (in_opt && accumulate && !nid_in_solve(c, sw) && !c->comm) {  // the next step's sumNID / numID (its backup idepths are this pass's)
         Pp.win_nid = c->win_nid();
         Pp.n_nid = c->n_win;
         Pp.nid_chunk = (int)std::min<size_t>(1024, (sc_smem / sizeof(float)) & ~(size_t)3);
     }
-    Sp.accumulate = accumulate;
-    Sp.pair_base = 0;
-    Sp.win_base = 0;
-    Sp.n_win = c->n_win;
     int kp_max = 0, n_max = 2;
     for (const WinDev &D : c->wd) {
         kp_max = std::max(kp_max, D.KP);
         n_max = std::max(n_max, D.N);
     }
-    Sp.frame_win = c->d_frame_win.p;
-    Sp.frame_base = 0;
     // two 512-thread blocks fit a CU: split the host blocks when the doubled grid still runs at once
     Sp.hs_split = Sp.n_win + 2 * c->n_frames <= 2 * c->n_cu ? 1 : 0;
-    if (const char *e = std::getenv("LDSO_BA_HS_SPLIT")) Sp.hs_split = e[0] == '1';  // tests: force either
-    const size_t st_smem = c->host_stitch ? stitch_host_smem_bytes(n_max, &Sp.th_cap)
-                                          : stitch_smem_bytes(kp_max, n_max, &Sp.th_cap);
+    if (sw.hs_split >= 0) Sp.hs_split = sw.hs_split;  // tests: force either
+    const bool hs = c->host_stitch;
+    const size_t st_smem = hs ? stitch_host_smem_bytes(n_max, &Sp.th_cap) : stitch_smem_bytes(kp_max, n_max, &Sp.th_cap);
     hipStream_t st = c->stream;
     if (L.n_items > 0) {
-        rc = timed_launch_ext(c, 0, st, [&](hipEvent_t a, hipEvent_t b) {
+        rc = timed_launch_ext(c, 0, [&](hipEvent_t a, hipEvent_t b) {
             if (c->marg) launch_linearize<true>(c->img_mode, L.n_blocks, st, L, a, b);
             else launch_linearize<false>(c->img_mode, L.n_blocks, st, L, a, b);
         });
@@ -5769,34 +5374,36 @@ int ldso_ba_linearize(ldso_ba_ctx *c, int32_t fix, int32_t accumulate) {
                           [&] { k_point_sc<<<Pp.n_nid + Pp.n_items, kScThreads, sc_smem, st>>>(Pp); });
         if (rc) return rc;
     }
-    if (c->host_stitch) {
+    if (hs) {
         static std::once_flag once;
         std::call_once(once, [] {
             int th;
             (void)hipFuncSetAttribute((const void *)k_stitch_host, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)stitch_host_smem_bytes(kHostStitchMaxN, &th));
         });
-        rc = timed_launch(c, 2, st, [&] { k_stitch_host<<<Sp.n_win + (Sp.hs_split ? 2 : 1) * c->n_frames, kHsThreads, st_smem, st>>>(Sp);
-        });
-        if (!rc && accumulate)
-            rc = timed_launch(c, 7, st, [&] {
-                k_stitch_host_sum<<<c->n_sum_blocks, 256, 0, st>>>(c->d_wins.p, c->d_sum_blocks.p, c->d_stage.p,
-                                                                   c->d_sys.p);
-            });
-    } else {
-        rc = timed_launch(c, 2, st, [&] { k_stitch<<<Sp.n_win + c->n_pairs, kStThreads, st_smem, st>>>(Sp); });
-        if (!rc && accumulate)
-            rc = timed_launch(c, 7, st, [&] {
-                k_stitch_sum<<<c->n_sum_blocks, 256, 0, st>>>(c->d_wins.p, c->d_sum_blocks.p, c->d_stage.p, c->d_sys.p);
-            });
     }
+    // a block per window, then per host frame (host stitch; two when split) or per frame pair (records)
+    const int st_grid = Sp.n_win + (hs ? (Sp.hs_split ? 2 : 1) * c->n_frames : c->n_pairs);
+    rc = timed_launch(c, 2, st, [&] {
+        if (hs) k_stitch_host<<<st_grid, kHsThreads, st_smem, st>>>(Sp);
+        else k_stitch<<<st_grid, kStThreads, st_smem, st>>>(Sp);
+    });
+    if (!rc && accumulate)
+        rc = timed_launch(c, 7, st, [&] {
+            if (hs) k_stitch_host_sum<<<c->n_sum_blocks, 256, 0, st>>>(c->d_wins.p, c->d_sum_blocks.p, c->d_stage.p, c->d_sys.p);
+            else k_stitch_sum<<<c->n_sum_blocks, 256, 0, st>>>(c->d_wins.p, c->d_sum_blocks.p, c->d_stage.p, c->d_sys.p);
+        });
     if (rc || !c->comm) return rc;
-    rc = comm_exchange(c, accumulate != 0);
+    rc = comm_exchange(c, accumulate != 0, sw);
     if (!rc && in_opt) {  // the reduced energies into the optimize() history
         k_energy_to_history<<<1, 256, 0, st>>>(c->win_energy(), c->d_ehist.p, c->opt_pass, 2 * c->n_win);
         HIP_TRY(hipGetLastError());
     }
     return rc;
+}
+
+int ldso_ba_linearize(ldso_ba_ctx *c, int32_t fix, int32_t accumulate) {
+    return linearize_pass(c, fix, accumulate, read_switches());
 }
 
 // k_record_jpjdf into d_jp_out and down to the host: [R][8] in device order
@@ -5842,16 +5449,7 @@ int ldso_ba_linearize_residuals(ldso_ba_ctx *c, int32_t win, int8_t *new_state, 
             reinterpret_cast<float *>(c->d_sx_center.p) + b, (long long)Rt, c->d_sx_flags.p + b, c->d_rs_flags.p + b);
         HIP_TRY(hipGetLastError());
     }
-    LinParams L{};
-    L.aff_fix = aff_fix_bits(c);
-    L.items = c->d_top_items.p;
-    L.wins = c->d_wins.p;
-    L.img = c->img_ext ? c->img_ext : c->d_img.p;
-    L.ad_ht_delta = nullptr;
-    L.precalc = c->d_precalc.p;
-    L.frame_th = c->d_frame_th.p;
-    L.rs_slot = c->d_rs_slot.p;
-    L.pt_data = c->d_pt_data.p;
+    LinParams L = lin_params(c);  // this window's items on the scratch state, nothing accumulated
     L.rs_state = c->d_sx_state.p;
     L.rs_newstate = c->d_sx_newstate.p;
     L.rs_flags = c->d_sx_flags.p;
@@ -5859,16 +5457,11 @@ int ldso_ba_linearize_residuals(ldso_ba_ctx *c, int32_t win, int8_t *new_state, 
     L.rs_newenergy = c->d_sx_newenergy.p;
     L.rs_energy_wo = c->d_sx_ewo.p;
     L.rs_center = reinterpret_cast<float *>(c->d_sx_center.p);
-    L.center_stride = (long long)Rt;
     L.rec_a = c->d_sx_rec_a.p;
     L.rec_b = c->d_sx_rec_b.p;
     L.geo_snap = c->d_sx_geo_snap.p;
     L.top_slab = nullptr;
     L.item_energy = c->d_sx_item.p;
-    L.frame_stride = c->frame_stride;
-    L.tiles_per_row = c->tiles_per_row;
-    L.fix = 0;
-    L.accumulate = 0;
     L.item_base = D.top_item_base;
     L.n_items = D.n_top_items;
     L.n_blocks = (L.n_items + 3) / 4;
@@ -5927,7 +5520,7 @@ int ldso_ba_activate_points(ldso_ba_ctx *c, int32_t win, int32_t n, const ldso_c
     HIP_TRY(hipMemcpyAsync(c->d_act_in.p, pts, (size_t)n * sizeof(ldso_ct_immature), hipMemcpyHostToDevice, c->stream));
     ActParams A;
     A.wins = c->d_wins.p;
-    A.img = c->img_ext ? c->img_ext : c->d_img.p;
+    A.img = c->images();
     A.precalc = c->d_precalc.p;
     A.pts = c->d_act_in.p;
     A.out = c->d_act_out.p;
@@ -5985,6 +5578,18 @@ int ldso_ba_get_energy(ldso_ba_ctx *c, int32_t win, double *out) {
     return 0;
 }
 
+// n point steps from point `base` on into pin_step (grown as needed), synchronised
+static int fetch_point_steps(ldso_ba_ctx *c, int base, int n) {
+    if (c->pin_step_n < (size_t)n) {
+        if (c->pin_step) (void)hipHostFree(c->pin_step);
+        c->pin_step = nullptr;
+        HIP_TRY(hipHostMalloc(&c->pin_step, std::max<size_t>(1, n) * sizeof(float), hipHostMallocDefault));
+        c->pin_step_n = n;
+    }
+    if (n) HIP_TRY(hipMemcpyAsync(c->pin_step, c->d_pt_step.p + base, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    return ldso_ba_sync(c);
+}
+
 // download one window's packed system (through pinned staging) unless the host copy is fresh
 static int fetch_sys(ldso_ba_ctx *c, int win) {
     if (!c->sys_host_valid) {
@@ -6022,7 +5627,6 @@ int ldso_ba_get_system(ldso_ba_ctx *c, int32_t win, double *HA, double *bA, doub
     int rc = fetch_sys(c, win);
     if (rc) return rc;
     const WinDev &D = c->wd[win];
-    const WinHost &H = c->wh[win];
     const int n = D.D;
     const long long pl = packed_len(n);
     const double *s = c->sys_host.data() + D.sys_base;
@@ -6032,25 +5636,14 @@ int ldso_ba_get_system(ldso_ba_ctx *c, int32_t win, double *HA, double *bA, doub
     if (bsc) std::memcpy(bsc, s + 2 * pl + n, n * sizeof(double));
     // HL / bL: accumulateLF_MT in the hot path has no linearized residuals, so it is exactly the
     // priors of stitchDoubleInternal(usePrior=true) (AccumulatedTopHessian.cc:241-250).
+    std::vector<double> pr;  // [q] = {HL(q, q), bL(q)}
+    if (HL || bL) priors_vector(c, win, pr);
     if (HL) {
         std::memset(HL, 0, sizeof(double) * n * n);
-        if (H.add_priors) {
-            for (int i = 0; i < 4; i++) HL[(size_t)i * n + i] = H.c_prior[i];
-            for (int f = 0; f < H.N; f++)
-                for (int i = 0; i < 8; i++) {
-                    const int q = 4 + 8 * f + i;
-                    HL[(size_t)q * n + q] = H.frame_prior[8 * f + i];
-                }
-        }
+        for (int q = 0; q < n; q++) HL[(size_t)q * n + q] = pr[2 * q];
     }
-    if (bL) {
-        std::memset(bL, 0, sizeof(double) * n);
-        if (H.add_priors) {
-            for (int i = 0; i < 4; i++) bL[i] = H.c_prior[i] * (double)H.c_delta[i];
-            for (int f = 0; f < H.N; f++)
-                for (int i = 0; i < 8; i++) bL[4 + 8 * f + i] = H.frame_prior[8 * f + i] * H.frame_delta_prior[8 * f + i];
-        }
-    }
+    if (bL)
+        for (int q = 0; q < n; q++) bL[q] = pr[2 * q + 1];
     return 0;
 }
 
@@ -6184,16 +5777,7 @@ int ldso_ba_resubstitute(ldso_ba_ctx *c, int32_t win, const double *x, double la
         if (rc) return rc;
     }
     if (point_step_out) {
-        if (c->pin_step_n < (size_t)D.P) {
-            if (c->pin_step) (void)hipHostFree(c->pin_step);
-            c->pin_step = nullptr;
-            HIP_TRY(hipHostMalloc(&c->pin_step, std::max<size_t>(1, D.P) * sizeof(float), hipHostMallocDefault));
-            c->pin_step_n = D.P;
-        }
-        if (D.P)
-            HIP_TRY(hipMemcpyAsync(c->pin_step, c->d_pt_step.p + D.point_base, D.P * sizeof(float),
-                                   hipMemcpyDeviceToHost, c->stream));
-        int rc = ldso_ba_sync(c);
+        int rc = fetch_point_steps(c, D.point_base, D.P);
         if (rc) return rc;
         for (int q = 0; q < D.P; q++) point_step_out[H.pt_orig[q]] = c->pin_step[q];
     }
@@ -6238,7 +5822,7 @@ inline bool ortho_x_later(const ldso_ba_ctx *c) {
 }
 // k_solve_fast (or the exact k_solve_reg / k_solve) for every loaded window; n_null > 0 projects
 // with the nullspaces upload_nullspaces prepared (iteration >= 2), n_null == 0 does not project
-int solve_device_launch(ldso_ba_ctx *c, int iteration, int n_null) {
+int solve_device_launch(ldso_ba_ctx *c, int iteration, int n_null, const Switches &sw) {
     int dmax = 0;
     for (const WinDev &D : c->wd) dmax = std::max(dmax, D.D);
     if (dmax > kSolveMaxDim) return fail(-1, "device solve supports windows of up to 11 keyframes");
@@ -6268,10 +5852,10 @@ int solve_device_launch(ldso_ba_ctx *c, int iteration, int n_null) {
         (void)hipFuncSetAttribute((const void *)k_solve_fast, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)solve_fast_smem_bytes(kSolveMaxDim));
     });
-    if (!c->solve_exact && !getenv_flag("LDSO_BA_SOLVE_LDS")) {  // the default: unpivoted, xAd fused
+    if (nid_in_solve(c, sw)) {  // the default: unpivoted, xAd fused; the sumNID chains run beside it
         const size_t smem = solve_fast_smem_bytes(dmax);
         int grid = c->n_win;
-        if (c->opt_pass >= 0 && nid_in_solve(c)) {  // the step's sumNID chains in blocks of their own
+        if (c->opt_pass >= 0) {  // the step's sumNID chains in blocks of their own
             S.win_nid = c->win_nid();
             S.nid_src = nid_source(c);
             S.n_win = c->n_win;
@@ -6281,7 +5865,7 @@ int solve_device_launch(ldso_ba_ctx *c, int iteration, int n_null) {
         return timed_launch(c, 5, c->stream, [&] { k_solve_fast<<<grid, kSolveFastThreads, smem, c->stream>>>(S); });
     }
     // exact mode: windows of up to 7 keyframes (n <= 64) the register factorisation, larger the LDS one
-    const bool reg = dmax <= kSolveRegDim && !getenv_flag("LDSO_BA_SOLVE_LDS");
+    const bool reg = dmax <= kSolveRegDim && !sw.solve_lds;
     const size_t smem = reg ? solve_reg_smem_bytes(dmax) : solve_smem_bytes(dmax);
     int rc = timed_launch(c, 5, c->stream, [&] {
         if (reg)
@@ -6311,7 +5895,7 @@ int ldso_ba_solve_device(ldso_ba_ctx *c, int32_t iteration, double lambda, const
     HIP_TRY(hipSetDevice(c->device));
     const bool project = iteration >= 2 && ns && n_null > 0 && ortho_x_later(c);
     if (project && (rc = upload_nullspaces(c, ns, n_null))) return rc;
-    rc = solve_device_launch(c, iteration, project ? n_null : 0);
+    rc = solve_device_launch(c, iteration, project ? n_null : 0, read_switches());
     if (rc) return rc;
     if (x_out) {
         HIP_TRY(hipMemcpyAsync(x_out, c->d_x.p, (size_t)c->vec_total * sizeof(double), hipMemcpyDeviceToHost,
@@ -6332,24 +5916,9 @@ int ldso_ba_resubstitute_device(ldso_ba_ctx *c, double lambda, float *point_step
         if (rc) return rc;
     }
     if (point_step_out) {
-        if (c->pin_step_n < (size_t)c->P_tot) {
-            if (c->pin_step) (void)hipHostFree(c->pin_step);
-            c->pin_step = nullptr;
-            HIP_TRY(hipHostMalloc(&c->pin_step, std::max<size_t>(1, c->P_tot) * sizeof(float), hipHostMallocDefault));
-            c->pin_step_n = c->P_tot;
-        }
-        if (c->P_tot)
-            HIP_TRY(hipMemcpyAsync(c->pin_step, c->d_pt_step.p, c->P_tot * sizeof(float), hipMemcpyDeviceToHost,
-                                   c->stream));
-        int rc = ldso_ba_sync(c);
+        int rc = fetch_point_steps(c, 0, c->P_tot);
         if (rc) return rc;
-        long long out_base = 0;  // windows back to back, each in its caller point order
-        for (int w = 0; w < c->n_win; w++) {
-            const WinDev &D = c->wd[w];
-            const WinHost &H = c->wh[w];
-            for (int q = 0; q < D.P; q++) point_step_out[out_base + H.pt_orig[q]] = c->pin_step[D.point_base + q];
-            out_base += H.P_all;
-        }
+        scatter_points(c, c->pin_step, point_step_out);
     }
     return 0;
 }
@@ -6358,14 +5927,13 @@ int ldso_ba_resubstitute_device(ldso_ba_ctx *c, double lambda, float *point_step
 namespace {
 // The launch parameters a captured pass / solve sequence depends on besides the call's own
 // arguments: the solve kernel (exact or fast), the stitch split, and every setting the kernels read.
-std::vector<unsigned long long> capture_key(const ldso_ba_ctx *c) {
-    const char *hs = std::getenv("LDSO_BA_HS_SPLIT");
+std::vector<unsigned long long> capture_key(const ldso_ba_ctx *c, const Switches &sw) {
     unsigned a, b, th;
     std::memcpy(&a, &c->settings.affine_opt_mode_a, 4);
     std::memcpy(&b, &c->settings.affine_opt_mode_b, 4);
     std::memcpy(&th, &c->settings.th_opt_iterations, 4);
-    return {(unsigned long long)c->solve_exact, (unsigned long long)getenv_flag("LDSO_BA_SOLVE_LDS"),
-            (unsigned long long)(hs ? (hs[0] == '1' ? 1 : 2) : 0), (unsigned long long)(unsigned)c->settings.solver_mode,
+    return {(unsigned long long)c->solve_exact, (unsigned long long)sw.solve_lds,
+            (unsigned long long)(sw.hs_split < 0 ? 0 : sw.hs_split == 1 ? 1 : 2), (unsigned long long)(unsigned)c->settings.solver_mode,
             (unsigned long long)(unsigned)c->settings.min_opt_iterations, a, b, th};
 }
 // Launch a captured sequence: replay g if it was captured under the current allocation
@@ -6419,20 +5987,21 @@ int ldso_ba_iterate(ldso_ba_ctx *c, int32_t iteration, double lambda, const doub
         return rc;
     // pass + solve + resubstitution (LDSO_BA_ITERATE_GRAPH=1: one captured graph per (projection,
     // lambda, n_null) without a communicator or kernel timing); the downloads stay outside it
+    const Switches sw = read_switches();  // one reading for the launches and the graph's key
     auto body = [&]() -> int {
         int r;
-        if ((r = ldso_ba_linearize(c, 0, 1))) return r;
-        if ((r = solve_device_launch(c, project ? 2 : 0, project ? n_null : 0))) return r;
+        if ((r = linearize_pass(c, 0, 1, sw))) return r;
+        if ((r = solve_device_launch(c, project ? 2 : 0, project ? n_null : 0, sw))) return r;
         return c->P_tot > 0 ? launch_resubstitute(c, 0, c->P_tot, lambda) : 0;
     };
     // direct launches by default: for this six-launch sequence hipGraphLaunch costs more host
     // time than it saves (one S7 window: 89 vs 95 us per call, tools/iter_probe.py)
-    if (!c->comm && !c->timing && getenv_flag("LDSO_BA_ITERATE_GRAPH") && !getenv_flag("LDSO_BA_NO_GRAPH")) {
+    if (!c->comm && !c->timing && sw.iterate_graph && !sw.no_graph) {
         unsigned long long lb;
         std::memcpy(&lb, &lambda, sizeof(lb));
         // keyed by everything fixed at capture: lambda, n_null, the solve kernel, the stitch split,
         // the settings the pass reads
-        std::vector<unsigned long long> key = capture_key(c);
+        std::vector<unsigned long long> key = capture_key(c, sw);
         key.push_back(lb);
         key.push_back((unsigned long long)n_null);
         rc = launch_cached_graph(c, c->it_graph[project ? 1 : 0], key, body);
@@ -6464,15 +6033,7 @@ int ldso_ba_iterate(ldso_ba_ctx *c, int32_t iteration, double lambda, const doub
     }
     if ((rc = ldso_ba_sync(c))) return rc;
     if (x_out) std::memcpy(x_out, px, xb);
-    if (point_step_out) {
-        long long out_base = 0;  // windows back to back, each in its caller point order
-        for (int w = 0; w < c->n_win; w++) {
-            const WinDev &D = c->wd[w];
-            const WinHost &H = c->wh[w];
-            for (int q = 0; q < D.P; q++) point_step_out[out_base + H.pt_orig[q]] = ps[D.point_base + q];
-            out_base += H.P_all;
-        }
-    }
+    if (point_step_out) scatter_points(c, ps, point_step_out);
     if (energy_out)
         for (int w = 0; w < c->n_win; w++) {
             energy_out[3 * w] = pe[2 * w];
@@ -6621,9 +6182,10 @@ int ldso_ba_optimize(ldso_ba_ctx *c, int32_t n_its, const ldso_ba_opt_settings *
     // one GN iteration: solveSystemF (a NaN x: the window is lost), resubstituteF_MT,
     // doStepFromBackup + setPrecalcValues (canbreak), linearizeAll + applyRes (+ the accumulation
     // the next solve uses); windows that left the loop skip every launch
+    const Switches sw = read_switches();  // one reading for the launches and the graph's key
     auto gn_iteration = [&](int it) -> int {
         int r;
-        if ((r = solve_device_launch(c, it, ns ? 7 : 0))) return r;
+        if ((r = solve_device_launch(c, it, ns ? 7 : 0, sw))) return r;
         // the frame / calibration step + FrameFramePrecalc and the resubstitution with the point
         // step applied in place, in one launch (the solve wrote x and xAd)
         FrameStepParams Fi = F;
@@ -6636,7 +6198,7 @@ int ldso_ba_optimize(ldso_ba_ctx *c, int32_t n_its, const ldso_ba_opt_settings *
              })))
             return r;
         c->opt_pass = it + 1;
-        return ldso_ba_linearize(c, 0, it + 1 < n_its ? 1 : 0);
+        return linearize_pass(c, 0, it + 1 < n_its ? 1 : 0, sw);
     };
     // FullSystem::optimize (FullSystem.cc:853-976) with setting_forceAceptStep: resetOOB, then
     // linearizeAll + applyRes, then the GN iterations.  Every launch argument of the whole
@@ -6651,14 +6213,14 @@ int ldso_ba_optimize(ldso_ba_ctx *c, int32_t n_its, const ldso_ba_opt_settings *
         HIP_TRY(hipMemsetAsync(c->d_stop.p, 0x7f, (size_t)nw * sizeof(int), c->stream));
         HIP_TRY(hipMemsetAsync(c->d_status.p, 0, (size_t)nw * sizeof(int), c->stream));
         c->opt_pass = 0;  // every pass of this call writes its energies into the history too
-        if ((r = ldso_ba_reset_oob(c, -1)) || (r = ldso_ba_linearize(c, 0, n_its > 0 ? 1 : 0))) return r;
+        if ((r = ldso_ba_reset_oob(c, -1)) || (r = linearize_pass(c, 0, n_its > 0 ? 1 : 0, sw))) return r;
         for (int it = 0; it < n_its; it++)
             if ((r = gn_iteration(it))) return r;
         return 0;
     };
-    const bool use_graph = !c->comm && !c->timing && !getenv_flag("LDSO_BA_NO_GRAPH");
+    const bool use_graph = !c->comm && !c->timing && !sw.no_graph;
     if (use_graph && c->opt_warm) {
-        std::vector<unsigned long long> key = capture_key(c);  // the settings were installed above
+        std::vector<unsigned long long> key = capture_key(c, sw);  // the settings were installed above
         key.push_back((unsigned long long)(unsigned)n_its);
         rc = launch_cached_graph(c, c->opt_graph[ns ? 1 : 0], key, body);
     } else {
@@ -6725,16 +6287,7 @@ int ldso_ba_optimize(ldso_ba_ctx *c, int32_t n_its, const ldso_ba_opt_settings *
     std::memcpy(c->wd.data(), po + o_w, wb);
     c->th_host.assign(reinterpret_cast<const float *>(po + o_t), reinterpret_cast<const float *>(po + o_t) + c->n_frames);
     c->th_host_valid = true;
-    if (idepth_out) {
-        const float *id = reinterpret_cast<const float *>(po + o_i);
-        long long out_base = 0;  // windows back to back, each in its caller point order
-        for (int w = 0; w < nw; w++) {
-            const WinDev &D = c->wd[w];
-            const WinHost &H = c->wh[w];
-            for (int q = 0; q < D.P; q++) idepth_out[out_base + H.pt_orig[q]] = id[D.point_base + q];
-            out_base += H.P_all;
-        }
-    }
+    if (idepth_out) scatter_points(c, reinterpret_cast<const float *>(po + o_i), idepth_out);
     c->sys_host_valid = false;
     c->energy_valid = false;
     return 0;

@@ -1,10 +1,15 @@
-# Build libldso_ba.so from ldso_ba.hip as of a git revision (the other sources from the tree):
-#   bash tools/build_ab_rev.sh NAME REV  ->  abl/NAME/libldso_ba.so
+# Build libldso_ba.so of a git revision from that revision's own ldso_amd/csrc (every source and
+# its Makefile), optionally with extra compiler flags and patches applied first, for
+# LDSO_BA_LIB / tools/ab_libs.py:
+#   bash tools/build_ab_rev.sh NAME REV ["-DFLAG=1 ..."] [PATCH ...]  ->  abl/NAME/libldso_ba.so
+# The recorded patches (tools/rejected/, tools/diag/) apply to the revision tools/rejected/README.md names.
 set -e
-cd "$(dirname "$0")/../ldso_amd/csrc"
-make -s ../lib/ldso_ct.o ../lib/host_math.o
-name=$1; rev=$2; out=../../abl/$name; mkdir -p $out
-git show $rev:ldso_amd/csrc/ldso_ba.hip > ldso_ba_rev_tmp.hip
-HIPFLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-slp-vectorize -Wall -Wno-unused-function -Wno-unused-result -Wno-unused-const-variable"
-/opt/rocm/bin/hipcc $HIPFLAGS -c -o $out/ldso_ba.o ldso_ba_rev_tmp.hip && rm -f ldso_ba_rev_tmp.hip
-/opt/rocm/bin/hipcc -shared --offload-arch=gfx950 -o $out/libldso_ba.so $out/ldso_ba.o ../lib/ldso_ct.o ../lib/host_math.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+cd "$(dirname "$0")/.."
+name=$1; rev=$2; flags=${3:-}; shift 2; [ $# -gt 0 ] && shift
+out=abl/$name/src
+mkdir -p $out
+git archive "$rev" ldso_amd/csrc include | tar -x -C $out
+for p in "$@"; do patch -s -p1 -d $out < "$p"; done
+base=$(sed -n 's/^HIPFLAGS ?= //p' $out/ldso_amd/csrc/Makefile)
+make -s -j4 -C $out/ldso_amd/csrc ../lib/libldso_ba.so HIPFLAGS="$base $flags"
+cp $out/ldso_amd/lib/libldso_ba.so abl/$name/libldso_ba.so

@@ -1,4 +1,4 @@
-# A/B of k_stitch_sum batch sizes (tools/build_ab.sh builds), one window and 64 windows
+# A/B of k_stitch_sum batch sizes (tools/build_ab_rev.sh builds), one window and 64 windows
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out

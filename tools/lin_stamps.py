@@ -1,6 +1,6 @@
 """Diagnostic: the batched pass (64 x S7) on a LDSO_LIN_STAMPS build of k_linearize
-(git apply tools/diag/k_linearize_stamps.patch; bash tools/build_ab.sh linstamps -DLDSO_LIN_STAMPS=1;
-LDSO_BA_LIB=abl/linstamps/libldso_ba.so): per-phase shader cycles of every 97th chunk --
+(bash tools/build_ab_rev.sh linstamps REV -DLDSO_LIN_STAMPS=1 tools/diag/k_linearize_stamps.patch, REV as
+in tools/rejected/README.md; LDSO_BA_LIB=abl/linstamps/libldso_ba.so): per-phase shader cycles of every 97th chunk --
 prologue (loads, LDS staging), phase A (pattern pixels), phase B (per residual), Top (MFMA block)."""
 import os
 import re

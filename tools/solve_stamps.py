@@ -1,8 +1,9 @@
 """Per-phase shader clocks of k_solve_fast (one S7 window, block 0, waves 0 and 1) from a diagnostic
-build (-DLDSO_SOLVE_STAMPS, tools/build_ab.sh): assembly, each panel's next-panel update / barrier /
+build (-DLDSO_SOLVE_STAMPS, tools/build_ab_rev.sh): assembly, each panel's next-panel update / barrier /
 panel factorisation (wave 0) or trailing update (wave 1) / barrier, back substitution, projection,
 xAd.  s_memtime ticks (shader clock, ~2.4 GHz).
-  git apply tools/rejected/solve_fast_strips_and_stamps_r6.patch && bash tools/build_ab.sh stamps -DLDSO_SOLVE_STAMPS
+  bash tools/build_ab_rev.sh stamps REV -DLDSO_SOLVE_STAMPS tools/rejected/solve_fast_strips_and_stamps_r6.patch
+  (REV as in tools/rejected/README.md)
   python tools/solve_stamps.py abl/stamps/libldso_ba.so [abl/strips/libldso_ba.so ...]"""
 import ctypes as C
 import json
