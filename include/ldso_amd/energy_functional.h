@@ -233,6 +233,21 @@ public:
     // ---- EnergyFunctional.h:55-186 -------------------------------------------------------
     void insertResidual(shared_ptr<PointFrameResidual> r);
     void insertFrame(shared_ptr<FrameHessian> fh, shared_ptr<CalibHessian> Hcalib);
+    // The same with the image handed over on the device: fh's level-0 image is the coarse tracker's
+    // current new frame (ldso_ct_set_new_frame ran on fh's image), copied device to device into the
+    // window's frame store; fh->dI may be null.  Needs resident frames (the default).
+    void insertFrame(shared_ptr<FrameHessian> fh, shared_ptr<CalibHessian> Hcalib, const ldso_ct_ctx *tracker);
+    // Resident frames (default on): every keyframe's image enters the device once -- at insertFrame,
+    // from fh->dI or from the tracker -- into the context's frame store under fh->frameID, leaves it
+    // at marginalizeFrame, and a structural change reloads the window by frame id
+    // (ldso_ba_load_frames) without touching the host images.  Off: the window's images are
+    // gathered on the host and uploaded by ldso_ba_load on every structural change, as before
+    // (kept for A/B and as the fallback).  If a host image's gradients are not makeImages', the
+    // store is re-reserved in image layout 1 and the window's frames are put again from their
+    // host dI, or, where that cannot be done, the window falls back to the off path: either way
+    // silently, as ldso_ba_load falls back.
+    void setResidentFrames(bool on);
+    bool residentFrames() const { return resident_; }
     void dropResidual(shared_ptr<PointFrameResidual> r);
     void marginalizeFrame(shared_ptr<FrameHessian> fh);
     void removePoint(shared_ptr<PointHessian> ph);
@@ -348,6 +363,10 @@ public:
 private:
     enum class ResSync { Synced, HostNewer, DeviceNewer };
     bool upload();
+    void insertFrameImpl(shared_ptr<FrameHessian> fh, shared_ptr<CalibHessian> Hcalib, const ldso_ct_ctx *tracker);
+    bool storeReserve();
+    bool storePutHost(const FrameHessian &fh);
+    bool storeHas(int frameID) const;
     bool uploadFrameTerms();
     bool runRelinearization();
     bool readBack(bool points_and_th);
@@ -379,6 +398,10 @@ private:
     float cDeltaUp_[4] = {0, 0, 0, 0};  // cDeltaF as last uploaded (it feeds the bL prior)
     std::vector<float> thUp_;
     int width_ = 0, height_ = 0;
+    // frame store: resident_ selects the path; the store's size as reserved and the frameIDs in it
+    bool resident_ = true;
+    int storeW_ = 0, storeH_ = 0;
+    std::vector<int> storeIds_;
     ResSync resSync_ = ResSync::Synced;
     long passes_ = 0;
     // the per-residual relinearisation (linearizeResidual): valid while epoch_ is unchanged and

@@ -235,6 +235,52 @@ int ldso_ba_comm_init(ldso_ba_ctx *ctx, const uint8_t *id, int32_t rank, int32_t
 int ldso_ba_load(ldso_ba_ctx *ctx, int32_t n_windows, const ldso_ba_window *windows,
                  int32_t shard_rank, int32_t shard_count);
 
+/* ---- device-resident frame store -------------------------------
+ * Keyframe images enter the device once, keyed by a caller frame id (FrameHessian::frameID), from
+ * the host (one frame) or device to device (the coarse tracker's new frame, any device buffer), and
+ * ldso_ba_load_frames names the windows' frames by id.  The window images the kernels read stay
+ * one contiguous array; each position carries the tag of the store slot it was copied from, and a
+ * load copies slot -> position on the context stream only where the tag differs.  ldso_ba_load
+ * keeps working beside the store (it invalidates the tags).
+ * Error codes of this group beyond -1 / -2 / -3: LDSO_BA_ERR_FRAME_STORE (store not reserved, full,
+ * id not resident, size mismatch) and LDSO_BA_ERR_GRADIENT_MISMATCH (below). */
+#define LDSO_BA_ERR_FRAME_STORE (-4)
+#define LDSO_BA_ERR_GRADIENT_MISMATCH (-5)
+struct ldso_ct_ctx;
+/* `capacity` image slots of width x height in the context's image layout (LDSO_BA_TUNE_TILED_IMAGES
+ * as set before this call; fixed for the store's life).  Re-reserving drops every resident frame. */
+int ldso_ba_frames_reserve(ldso_ba_ctx *ctx, int32_t capacity, int32_t width, int32_t height);
+/* Host FrameHessian::dI [h*w][3] -> the slot of frame_id (a new slot, or overwritten if resident):
+ * one copy through the context's pinned staging, then the load's repack kernel.  In layout 3 the
+ * gradients must be makeImages' (the layout recomputes them): if not, the call returns
+ * LDSO_BA_ERR_GRADIENT_MISMATCH, the frame is not resident afterwards and the layout is NOT
+ * switched -- reserve the store in layout 1 (LDSO_BA_TUNE_TILED_IMAGES = 1) for such frames. */
+int ldso_ba_frame_put(ldso_ba_ctx *ctx, int64_t frame_id, const float *dI);
+/* Device source: intensity plane [h*w] row-major and/or texels [h*w] float4 {I, dx, dy, *}, produced
+ * on producer_stream (hipStream_t, NULL = the null stream).  Layout 3 reads `intensity` (texels may
+ * be NULL) and does NOT check gradients: the contract is that the frame's gradients are
+ * makeImages', which is what layout 3 recomputes.  Layout 1 needs `texels`.  No host
+ * synchronisation: the ingest waits on the producer's stream by event, and work queued on
+ * producer_stream after this call waits for the ingest to have read the buffers. */
+int ldso_ba_frame_put_device(ldso_ba_ctx *ctx, int64_t frame_id, const float *dev_intensity,
+                             const void *dev_texels, void *producer_stream);
+/* The tracker's current new frame (ldso_ct_set_new_frame), level 0, device to device; the tracker's
+ * next ldso_ct_set_new_frame is ordered after the ingest. */
+int ldso_ba_frame_put_tracker(ldso_ba_ctx *ctx, int64_t frame_id, const struct ldso_ct_ctx *tracker);
+int ldso_ba_frame_drop(ldso_ba_ctx *ctx, int64_t frame_id);
+/* Read a resident frame back (test / debug; synchronises): intensity [h*w]; grad [h*w][2] only in
+ * layout 1 (else it must be NULL). */
+int ldso_ba_frame_get(ldso_ba_ctx *ctx, int64_t frame_id, float *intensity, float *grad);
+/* ldso_ba_load with the windows' frames named by id: frame_ids [sum N], the windows' frames back to
+ * back; windows[i].dI is ignored (may be NULL).  An id that is not resident fails with
+ * LDSO_BA_ERR_FRAME_STORE and a message naming it before anything on the device changes. */
+int ldso_ba_load_frames(ldso_ba_ctx *ctx, int32_t n_windows, const ldso_ba_window *windows,
+                        const int64_t *frame_ids, int32_t shard_rank, int32_t shard_count);
+/* out[4] = image bytes host -> device, image bytes device -> device, image buffer (re)allocations
+ * (window images, store, staging), frames ingested -- cumulative per context, counted at the
+ * library's own call sites (ldso_ba_load counts too). */
+int ldso_ba_transfer_stats(ldso_ba_ctx *ctx, int64_t out[4]);
+
 /* Refresh per-iteration state of window `win` after doStepFromBackup / setPrecalcValues:
  * precalc, adjoints, priors, cDeltaF, frame_energy_th and point_data (all 24 floats per point;
  * w->point_data == NULL leaves the points as they are, see ldso_ba_update_points).

@@ -204,7 +204,17 @@ ABI = [
     ("ldso_ba_load_marginalization", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(LdsoBaWindow)]),
     ("ldso_ba_marginalize_points", C.c_int, [C.c_void_p, f32p, f64p, f64p]),
     ("ldso_ba_activate_points", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    # device-resident frame store
+    ("ldso_ba_frames_reserve", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    ("ldso_ba_frame_put", C.c_int, [C.c_void_p, C.c_int64, f32p]),
+    ("ldso_ba_frame_put_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("ldso_ba_frame_put_tracker", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    ("ldso_ba_frame_drop", C.c_int, [C.c_void_p, C.c_int64]),
+    ("ldso_ba_frame_get", C.c_int, [C.c_void_p, C.c_int64, f32p, f32p]),
+    ("ldso_ba_load_frames", C.c_int, [C.c_void_p, C.c_int32, C.POINTER(LdsoBaWindow), i64p, C.c_int32, C.c_int32]),
+    ("ldso_ba_transfer_stats", C.c_int, [C.c_void_p, i64p]),
 ]
+ERR_FRAME_STORE, ERR_GRADIENT_MISMATCH = -4, -5
 
 f32pp = C.POINTER(f32p)
 
@@ -268,9 +278,17 @@ def lib():
     return _lib
 
 
+class LdsoError(RuntimeError):
+    """A negative return of the C ABI; ``code`` is that return."""
+
+    def __init__(self, code, msg):
+        super().__init__(f"ldso_ba error {code}: {msg}")
+        self.code = int(code)
+
+
 def check(rc):
     if rc != 0:
-        raise RuntimeError(f"ldso_ba error {rc}: {lib().ldso_ba_last_error().decode()}")
+        raise LdsoError(rc, lib().ldso_ba_last_error().decode())
     return rc
 
 

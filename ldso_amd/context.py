@@ -25,6 +25,7 @@ class BAContext:
         self._h = h
         self.windows: list[Window] = []
         self._structs = None
+        self._frame_shape = None  # (height, width) of the frame store once reserved
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -50,16 +51,96 @@ class BAContext:
         return out
 
     # ---- structure ---------------------------------------------------------------------
-    def load(self, windows, shard_rank: int = 0, shard_count: int = 1):
+    def load(self, windows, shard_rank: int = 0, shard_count: int = 1, *, frame_ids=None):
+        """ldso_ba_load, or with frame_ids (the windows' frames back to back, as frame-store ids)
+        ldso_ba_load_frames: the images come from the store and the windows' dI is not read (may be
+        None).  A failed load leaves the context's windows as they were."""
         if isinstance(windows, Window):
             windows = [windows]
-        self.windows = list(windows)
-        structs = (L.LdsoBaWindow * len(self.windows))(*[w.c_struct() for w in self.windows])
-        L.check(self._lib.ldso_ba_load(self._h, len(self.windows), structs, int(shard_rank), int(shard_count)))
+        windows = list(windows)
+        if frame_ids is None:
+            structs = (L.LdsoBaWindow * len(windows))(*[w.c_struct() for w in windows])
+            L.check(self._lib.ldso_ba_load(self._h, len(windows), structs, int(shard_rank), int(shard_count)))
+        else:
+            ids = np.ascontiguousarray(np.asarray(frame_ids).reshape(-1), np.int64)
+            assert ids.size == sum(w.n_frames for w in windows), "one frame id per frame of every window"
+            structs = (L.LdsoBaWindow * len(windows))(*[w.c_struct(with_images=False) for w in windows])
+            L.check(self._lib.ldso_ba_load_frames(self._h, len(windows), structs, L.ptr(ids, L.i64p), int(shard_rank),
+                                                  int(shard_count)))
+        self.windows = windows
         self._structs = structs
         for w in self.windows:
             w._keep = []  # host copies are no longer referenced by the device
         return self
+
+    # ---- device-resident frame store -----------------------------------------------------
+    def frames_reserve(self, capacity: int, width: int, height: int):
+        """ldso_ba_frames_reserve: `capacity` image slots in the context's image layout
+        (set_tuning(TILED_IMAGES) before this call).  Re-reserving drops every resident frame."""
+        L.check(self._lib.ldso_ba_frames_reserve(self._h, int(capacity), int(width), int(height)))
+        self._frame_shape = (int(height), int(width))
+        return self
+
+    def frame_put(self, frame_id: int, dI):
+        """Host FrameHessian::dI [h*w][3] -> the slot of frame_id.  In layout 3 gradients that are
+        not makeImages' raise with code L.ERR_GRADIENT_MISMATCH (reserve the store in layout 1)."""
+        a = np.ascontiguousarray(dI, np.float32).reshape(-1)
+        assert self._frame_shape is None or a.size == self._npix() * 3, "dI must be [h*w][3]"
+        L.check(self._lib.ldso_ba_frame_put(self._h, int(frame_id), L.ptr(a, L.f32p)))
+
+    def _npix(self) -> int:
+        if self._frame_shape is None:  # the library refuses the call itself, with its message
+            return 0
+        return self._frame_shape[0] * self._frame_shape[1]
+
+    @staticmethod
+    def _dev_ptr(x, n_floats):
+        """Raw device pointer of a torch CUDA tensor (float32, contiguous, n_floats elements) or an int."""
+        if x is None:
+            return None
+        if isinstance(x, int):
+            return C.c_void_p(x)
+        import torch
+
+        assert isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous(), \
+            "device sources are contiguous float32 CUDA tensors or raw pointers"
+        assert not n_floats or x.numel() == n_floats, f"tensor of {x.numel()} floats where {n_floats} are read"
+        return C.c_void_p(x.data_ptr())
+
+    def frame_put_device(self, frame_id: int, intensity=None, texels=None, stream=None):
+        """ldso_ba_frame_put_device: intensity [h*w] and / or texels [h*w][4] {I, dx, dy, *} on the
+        device (torch CUDA tensors or raw pointers), produced on `stream` (a torch stream, a raw
+        hipStream_t or None = torch's current stream when a tensor is given, else the null stream).
+        No host synchronisation; the tensors must stay alive until the stream work has run."""
+        n = self._npix()
+        if stream is None and not all(isinstance(x, (int, type(None))) for x in (intensity, texels)):
+            import torch
+
+            stream = torch.cuda.current_stream()
+        sp = getattr(stream, "cuda_stream", stream)
+        L.check(self._lib.ldso_ba_frame_put_device(self._h, int(frame_id), self._dev_ptr(intensity, n),
+                                                   self._dev_ptr(texels, n * 4), C.c_void_p(int(sp or 0))))
+
+    def frame_put_tracker(self, frame_id: int, tracker):
+        """The tracker's current new frame (CoarseTracker.set_new_frame), device to device."""
+        L.check(self._lib.ldso_ba_frame_put_tracker(self._h, int(frame_id), tracker._h))
+
+    def frame_drop(self, frame_id: int):
+        L.check(self._lib.ldso_ba_frame_drop(self._h, int(frame_id)))
+
+    def frame_get(self, frame_id: int, with_grad: bool = False):
+        """A resident frame back on the host: intensity [h*w], and grad [h*w][2] (layout 1 only)."""
+        n = max(self._npix(), 1)
+        inten = np.zeros(n, np.float32)
+        grad = np.zeros((n, 2), np.float32) if with_grad else None
+        L.check(self._lib.ldso_ba_frame_get(self._h, int(frame_id), L.ptr(inten, L.f32p), L.ptr(grad, L.f32p)))
+        return (inten, grad) if with_grad else inten
+
+    def transfer_stats(self) -> dict:
+        """Cumulative image traffic of this context (ldso_ba_transfer_stats)."""
+        o = np.zeros(4, np.int64)
+        L.check(self._lib.ldso_ba_transfer_stats(self._h, L.ptr(o, L.i64p)))
+        return dict(h2d_bytes=int(o[0]), d2d_bytes=int(o[1]), allocs=int(o[2]), frames=int(o[3]))
 
     def optimize(self, n_its: int, calib_value=None, calib_value_zero=None, nullspaces=None, settings=None):
         """FullSystem::optimize on the device (ldso_ba_optimize): up to n_its GN iterations of every

@@ -228,6 +228,97 @@ void EnergyFunctional::insertResidual(shared_ptr<PointFrameResidual> r) {
 
 // EnergyFunctional.cc:51-98 (the non-VI part): HM, bM grow by the frame's 8 zero rows/columns
 void EnergyFunctional::insertFrame(shared_ptr<FrameHessian> fh, shared_ptr<CalibHessian> Hcalib) {
+    insertFrameImpl(fh, Hcalib, nullptr);
+}
+void EnergyFunctional::insertFrame(shared_ptr<FrameHessian> fh, shared_ptr<CalibHessian> Hcalib, const ldso_ct_ctx *tracker) {
+    if (!tracker) {
+        err_ = "insertFrame: null tracker";
+        return;
+    }
+    if (!resident_) {
+        err_ = "insertFrame from the tracker needs resident frames (setResidentFrames(true))";
+        return;
+    }
+    insertFrameImpl(fh, Hcalib, tracker);
+}
+
+bool EnergyFunctional::storeHas(int frameID) const {
+    return std::find(storeIds_.begin(), storeIds_.end(), frameID) != storeIds_.end();
+}
+
+// LDSO_BA_MAX_FRAMES + 1 slots of the current image size: the window plus the frame that enters
+// before the marginalised one has left.  Re-reserving (another size) drops every resident frame.
+bool EnergyFunctional::storeReserve() {
+    if (storeW_ == width_ && storeH_ == height_) return true;
+    storeIds_.clear();
+    storeW_ = storeH_ = 0;
+    if (ldso_ba_frames_reserve(ctx_, LDSO_BA_MAX_FRAMES + 1, width_, height_)) {
+        fail("ldso_ba_frames_reserve");
+        return false;
+    }
+    storeW_ = width_;
+    storeH_ = height_;
+    return true;
+}
+
+// fh.dI into the store.  Gradients that are not makeImages' (image layout 3 recomputes them) keep
+// ldso_ba_load's silent fallback: the store is reserved again in layout 1 and the window's frames
+// put again from their host dI; where that is not possible (the layout is fixed once a window is
+// loaded, or a frame has no host image) the window goes back to ldso_ba_load, which falls back itself.
+bool EnergyFunctional::storePutHost(const FrameHessian &fh) {
+    if (!fh.dI) {
+        err_ = "frame " + std::to_string(fh.frameID) + " has no host dI and was not handed over from the tracker";
+        return false;
+    }
+    const int rc = ldso_ba_frame_put(ctx_, fh.frameID, fh.dI);
+    if (rc == 0) {
+        if (!storeHas(fh.frameID)) storeIds_.push_back(fh.frameID);
+        return true;
+    }
+    if (rc != LDSO_BA_ERR_GRADIENT_MISMATCH) {
+        fail("ldso_ba_frame_put");
+        return false;
+    }
+    bool all_host = true;
+    for (const shared_ptr<FrameHessian> &f : frames) all_host = all_host && f->dI;
+    if (all_host && ldso_ba_set_tuning(ctx_, LDSO_BA_TUNE_TILED_IMAGES, 1) == 0) {
+        storeW_ = storeH_ = 0;
+        if (!storeReserve()) return false;
+        for (const shared_ptr<FrameHessian> &f : frames) {
+            if (ldso_ba_frame_put(ctx_, f->frameID, f->dI)) {
+                fail("ldso_ba_frame_put (layout 1)");
+                return false;
+            }
+            storeIds_.push_back(f->frameID);
+        }
+        if (!storeHas(fh.frameID)) {  // fh is not in the window yet
+            if (ldso_ba_frame_put(ctx_, fh.frameID, fh.dI)) {
+                fail("ldso_ba_frame_put (layout 1)");
+                return false;
+            }
+            storeIds_.push_back(fh.frameID);
+        }
+        return true;
+    }
+    if (!all_host) {
+        err_ = "frame " + std::to_string(fh.frameID) + ": gradients are not makeImages' and a frame of the window has no host dI";
+        return false;
+    }
+    resident_ = false;
+    dirty_ = true;
+    return true;
+}
+
+void EnergyFunctional::setResidentFrames(bool on) {
+    if (on == resident_) return;
+    residualTouched();
+    resident_ = on;
+    dirty_ = true;  // the next pass reloads the window through the chosen path
+    epoch_++;
+}
+
+void EnergyFunctional::insertFrameImpl(shared_ptr<FrameHessian> fh, shared_ptr<CalibHessian> Hcalib,
+                                       const ldso_ct_ctx *tracker) {
     residualTouched();
     fh->takeData(&settings_);
     frames.push_back(fh);
@@ -245,6 +336,14 @@ void EnergyFunctional::insertFrame(shared_ptr<FrameHessian> fh, shared_ptr<Calib
     calib_ = *Hcalib;
     width_ = Hcalib->wG0;
     height_ = Hcalib->hG0;
+    if (resident_ && ctx_ && storeReserve()) {
+        if (tracker) {
+            if (ldso_ba_frame_put_tracker(ctx_, fh->frameID, tracker)) fail("ldso_ba_frame_put_tracker");
+            else if (!storeHas(fh->frameID)) storeIds_.push_back(fh->frameID);
+        } else {
+            storePutHost(*fh);
+        }
+    }
     setAdjointsF(Hcalib);
     makeIDX();
     for (const shared_ptr<FrameHessian> &fh2 : frames) {
@@ -297,6 +396,10 @@ void EnergyFunctional::marginalizeFrame(shared_ptr<FrameHessian> fh) {
     }
     HM = Ho;
     bM = bo;
+    if (storeHas(fh->frameID)) {
+        storeIds_.erase(std::find(storeIds_.begin(), storeIds_.end(), fh->frameID));
+        if (ldso_ba_frame_drop(ctx_, fh->frameID)) fail("ldso_ba_frame_drop");
+    }
     for (size_t i = (size_t)fh->idx; i + 1 < frames.size(); i++) {
         frames[i] = frames[i + 1];
         frames[i]->idx = (int)i;
@@ -621,10 +724,29 @@ bool EnergyFunctional::upload() {
     w.width = width_;
     w.height = height_;
     std::memcpy(w.calib, calib_.value_scaledf, sizeof(w.calib));
-    dI_.resize((size_t)N * width_ * height_ * 3);
-    for (int f = 0; f < N; f++)
-        std::memcpy(&dI_[(size_t)f * width_ * height_ * 3], frames[f]->dI, (size_t)width_ * height_ * 3 * sizeof(float));
-    w.dI = dI_.data();
+    // the images: by frame id out of the store (frames missing there -- the path was switched on
+    // with the window in place, or the store was reserved again -- go in now from their host dI), or
+    // gathered on the host for ldso_ba_load
+    std::vector<int64_t> ids;
+    if (resident_) {
+        if (!storeReserve()) return false;
+        for (int f = 0; f < N && resident_; f++)
+            if (!storeHas(frames[f]->frameID) && !storePutHost(*frames[f])) return false;
+    }
+    if (resident_) {
+        for (int f = 0; f < N; f++) ids.push_back(frames[f]->frameID);
+        std::vector<float>().swap(dI_);
+    } else {
+        dI_.resize((size_t)N * width_ * height_ * 3);
+        for (int f = 0; f < N; f++) {
+            if (!frames[f]->dI) {
+                err_ = "frame " + std::to_string(frames[f]->frameID) + " has no host dI (handed over from the tracker): ldso_ba_load needs it";
+                return false;
+            }
+            std::memcpy(&dI_[(size_t)f * width_ * height_ * 3], frames[f]->dI, (size_t)width_ * height_ * 3 * sizeof(float));
+        }
+        w.dI = dI_.data();
+    }
     w.frame_energy_th = frameTH_.data();
     w.precalc = precalc_.data();
     w.ad_host = adH_.data();
@@ -641,8 +763,8 @@ bool EnergyFunctional::upload() {
     w.res_energy = resEnergy_.data();
     w.res_flags = resFlags_.data();
     w.point_rank = pointRanked_ ? pointRank_.data() : nullptr;
-    if (ldso_ba_load(ctx_, 1, &w, 0, 1)) {
-        fail("ldso_ba_load");
+    if (resident_ ? ldso_ba_load_frames(ctx_, 1, &w, ids.data(), 0, 1) : ldso_ba_load(ctx_, 1, &w, 0, 1)) {
+        fail(resident_ ? "ldso_ba_load_frames" : "ldso_ba_load");
         return false;
     }
     // the device's state_NewEnergy starts as state_energy (ldso_ba_load); the host's may differ

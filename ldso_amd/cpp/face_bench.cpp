@@ -19,16 +19,26 @@
 //   c_abi_optimize  ldso_ba_optimize(6) on a context loaded with the same window (no face)
 //   flag_loop       FullSystem::flagPointsForRemoval's per-residual resetOOB / linearize /
 //                   applyRes over every residual of 10 % of the points (one device pass)
+//   keyframe_cycle  one keyframe's structural round on a window of its own: insertFrame + its
+//                   residuals, optimize(6), dropResidual of those residuals, marginalizeFrame; host
+//                   clock per cycle (median, min, max over the repetitions), once with resident
+//                   frames (the image enters the frame store once, the reload names frames by id) and
+//                   once with setResidentFrames(false) (every reload gathers and uploads all images),
+//                   each with its ldso_ba_transfer_stats deltas per cycle; ingest_us: one
+//                   ldso_ba_frame_put_tracker of a 640x480 frame, host clock over a back-to-back run
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <memory>
 #include <random>
+#include <string>
 #include <type_traits>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/ldso_amd/energy_functional.h"
+#include "../../include/ldso_ct.h"
 #include "../csrc/synth.h"
 
 using namespace ldso_amd;
@@ -373,6 +383,128 @@ int main(int argc, char **argv) {
         ms_raw = ms_since(t0) / reps;
         ldso_ba_destroy(raw);
     }
+    // keyframe_cycle: frames 0..5 and their points stay; frame 6 enters and leaves once per cycle
+    struct CycleResult {
+        double med = -1, lo = -1, hi = -1;
+        double xfer[4] = {0, 0, 0, 0};
+        bool ok = false;
+    };
+    auto keyframe_cycle = [&](bool resident) {
+        CycleResult out;
+        auto e2 = std::make_shared<EnergyFunctional>(0);
+        if (!e2->ok()) return out;
+        e2->setResidentFrames(resident);
+        auto make_frame = [&](int f, int id) {
+            auto F = std::make_shared<FrameHessian>();
+            F->frameID = id;
+            std::memcpy(F->worldToCam_evalPT, fs[f].world_to_cam_evalpt, sizeof(F->worldToCam_evalPT));
+            std::memcpy(F->state, fs[f].state, sizeof(F->state));
+            std::memcpy(F->state_zero, fs[f].state_zero, sizeof(F->state_zero));
+            F->ab_exposure = fs[f].ab_exposure;
+            F->dI = &dI[(size_t)f * W * H * 3];
+            F->frameEnergyTH = th[f];
+            return F;
+        };
+        std::vector<shared_ptr<FrameHessian>> fr;
+        for (int f = 0; f < N - 1; f++) {
+            fr.push_back(make_frame(f, f));
+            e2->insertFrame(fr.back(), HCalib);
+        }
+        std::vector<shared_ptr<PointHessian>> pts;
+        for (int p = 0; p < P; p++) {
+            if (ph[p] == N - 1) continue;
+            auto Pt = std::make_shared<PointHessian>();
+            const float *d = &pd[(size_t)p * LDSO_BA_POINT_STRIDE];
+            Pt->host = fr[ph[p]];
+            Pt->u = d[0];
+            Pt->v = d[1];
+            Pt->setIdepth(d[2]);
+            Pt->setIdepthZero(d[3]);
+            std::memcpy(Pt->color, d + 8, sizeof(Pt->color));
+            std::memcpy(Pt->weights, d + 16, sizeof(Pt->weights));
+            for (int k = rb[p]; k < rb[p + 1]; k++) {
+                if (rt[k] == N - 1) continue;
+                auto r = std::make_shared<PointFrameResidual>(Pt, fr[ph[p]], fr[rt[k]]);
+                r->isNew = true;
+                Pt->residuals.push_back(r);
+            }
+            pts.push_back(Pt);
+            e2->insertPoint(Pt);
+            for (auto &r : Pt->residuals) e2->insertResidual(r);
+        }
+        const int warm = 2;
+        std::vector<double> ms;
+        int64_t x0[4] = {0, 0, 0, 0}, x1[4] = {0, 0, 0, 0};
+        for (int c = 0; c < warm + reps && e2->ok(); c++) {
+            if (c == warm) ldso_ba_transfer_stats(e2->context(), x0);
+            auto F = make_frame(N - 1, 100 + c);
+            std::vector<shared_ptr<PointFrameResidual>> added;
+            auto t1 = Clock::now();
+            e2->insertFrame(F, HCalib);
+            for (auto &Pt : pts) {
+                auto r = std::make_shared<PointFrameResidual>(Pt, Pt->host.lock(), F);
+                r->isNew = true;
+                Pt->residuals.push_back(r);
+                e2->insertResidual(r);
+                added.push_back(r);
+            }
+            e2->makeIDX();
+            e2->setAdjointsF(HCalib);
+            e2->setDeltaF(HCalib);
+            e2->optimize(n_its, HCalib, nullptr, nullptr, nullptr, &all_its);
+            for (auto &r : added) e2->dropResidual(r);
+            e2->marginalizeFrame(F);
+            if (c >= warm) ms.push_back(ms_since(t1));
+        }
+        ldso_ba_transfer_stats(e2->context(), x1);
+        if (!e2->ok() || ms.empty()) {
+            std::fprintf(stderr, "keyframe_cycle: %s\n", e2->lastError().c_str());
+            return out;
+        }
+        std::sort(ms.begin(), ms.end());
+        out.med = ms[ms.size() / 2];
+        out.lo = ms.front();
+        out.hi = ms.back();
+        for (int i = 0; i < 4; i++) out.xfer[i] = (double)(x1[i] - x0[i]) / (double)ms.size();
+        out.ok = true;
+        return out;
+    };
+    const CycleResult kc_res = keyframe_cycle(true), kc_leg = keyframe_cycle(false);
+    // one device-to-device ingest of the tracker's new frame (event record / wait, the layout-3
+    // kernel): back to back on the host clock, one synchronisation at the end
+    double ingest_us = -1;
+    {
+        ldso_ct_ctx *ct = nullptr;
+        ldso_ba_ctx *bc = nullptr;
+        int32_t nl = 0;
+        std::vector<float> color((size_t)W * H);
+        for (size_t i = 0; i < color.size(); i++) color[i] = dI[3 * i];
+        if (ldso_ct_create(0, W, H, &ct, &nl) == 0 && ldso_ba_create(0, &bc) == 0 &&
+            ldso_ba_frames_reserve(bc, 2, W, H) == 0 && ldso_ct_set_new_frame(ct, color.data(), 1.0, nullptr) == 0) {
+            const int n_put = 200;
+            bool good = true;
+            for (int i = 0; i < 10; i++) good = good && ldso_ba_frame_put_tracker(bc, 1, ct) == 0;
+            ldso_ba_sync(bc);
+            auto t1 = Clock::now();
+            for (int i = 0; i < n_put; i++) good = good && ldso_ba_frame_put_tracker(bc, 1, ct) == 0;
+            ldso_ba_sync(bc);
+            if (good) ingest_us = 1000.0 * ms_since(t1) / n_put;
+        }
+        if (bc) ldso_ba_destroy(bc);
+        if (ct) ldso_ct_destroy(ct);
+    }
+    auto cycle_json = [](const CycleResult &r) {
+        char buf[512];
+        std::snprintf(buf, sizeof(buf),
+                      "{\"ok\": %s, \"ms_median\": %.6f, \"ms_min\": %.6f, \"ms_max\": %.6f, "
+                      "\"h2d_image_bytes_per_cycle\": %.1f, \"d2d_image_bytes_per_cycle\": %.1f, "
+                      "\"image_allocs_per_cycle\": %.3f, \"frames_ingested_per_cycle\": %.3f}",
+                      r.ok ? "true" : "false", r.med, r.lo, r.hi, r.xfer[0], r.xfer[1], r.xfer[2], r.xfer[3]);
+        return std::string(buf);
+    };
+    const std::string kc_json = "{\"what\": \"S7: insertFrame + residuals, optimize(6), dropResidual, marginalizeFrame; host clock\", "
+                                "\"resident\": " + cycle_json(kc_res) + ", \"legacy\": " + cycle_json(kc_leg) +
+                                ", \"ingest_us\": " + std::to_string(ingest_us) + "}";
     std::printf(
         "{\"window\": \"S7 (7 KF, 2000 pts, 640x480, seed 1)\", \"n_its\": %d, \"reps\": %d, \"ok\": %s, "
         "\"optimize\": {\"ms_per_optimize\": %.6f, \"ms_per_gn_iteration\": %.6f, \"iterations\": %d, "
@@ -387,10 +519,11 @@ int main(int argc, char **argv) {
         "\"optimize_full\": {\"ms\": %.6f, \"what\": \"optimize(6) + setAdjointsF + setDeltaF + linearizeAll(true) "
         "with the residual / point write-back\"}, "
         "\"c_abi_optimize\": {\"ms_per_optimize\": %.6f, \"ms_per_gn_iteration\": %.6f}, "
-        "\"flag_loop\": {\"residuals\": %d, \"ms\": %.6f, \"device_passes\": %ld}}\n",
+        "\"flag_loop\": {\"residuals\": %d, \"ms\": %.6f, \"device_passes\": %ld}, "
+        "\"keyframe_cycle\": %s}\n",
         n_its, reps, ok ? "true" : "false", ms_opt, ms_opt / n_its, n_its, its_default, (int)vr.size(), (int)ef->allPoints.size(),
         ms_shim_digest, ms_shim_vec, ms_shim_map, ms_shim_digest / n_its, ms_shim_digest / ms_opt, ms_shim_vec / ms_opt,
         toRemove.size(),
-        ms_full, ms_raw, ms_raw / n_its, nres, ms_flag, flag_passes);
+        ms_full, ms_raw, ms_raw / n_its, nres, ms_flag, flag_passes, kc_json.c_str());
     return ok ? 0 : 1;
 }

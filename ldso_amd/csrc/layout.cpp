@@ -69,9 +69,9 @@ void shard_points(const ldso_ba_window &in, int rank, int count, std::vector<int
 }
 
 int build_layout(const ldso_ba_window *ws, int n_windows, int shard_rank, int shard_count, int item_order,
-                 int top_chunk, bool marg, Layout &out) {
+                 int top_chunk, bool marg, Layout &out, bool resident_frames) {
     for (int w = 0; w < n_windows; w++) {
-        int rc = check_window(ws[w], !marg);
+        int rc = check_window(ws[w], !marg && !resident_frames);
         if (rc) return rc;
         if (ws[w].width != ws[0].width || ws[w].height != ws[0].height)
             return set_error(-1, "all windows of a context must share the image size");

@@ -94,8 +94,10 @@ void shard_points(const ldso_ba_window &in, int rank, int count, std::vector<int
 // Checks every window (images are not needed for a marginalisation context) and lays out this
 // shard of them.  item_order: ldso_ba_set_tuning's LDSO_BA_TUNE_ITEM_ORDER; top_chunk: its
 // LDSO_BA_TUNE_TOP_CHUNK (0 = by load size); marg: a marginalisation context (priorF scaled by
-// setting_idepthFixPriorMargFac).  Returns 0, or -1 with the thread's error message set.
+// setting_idepthFixPriorMargFac); resident_frames: the frames are named by frame-store ids
+// (ldso_ba_load_frames), so the windows' dI is not needed either.  Returns 0, or -1 with the
+// thread's error message set.
 int build_layout(const ldso_ba_window *ws, int n_windows, int shard_rank, int shard_count, int item_order,
-                 int top_chunk, bool marg, Layout &out);
+                 int top_chunk, bool marg, Layout &out, bool resident_frames = false);
 
 }  // namespace ldso_ba

@@ -27,8 +27,9 @@
 //
 // Outside the pass: the device solve (k_solve_fast; exact mode k_solve_reg / k_solve), k_step_resub
 // (doStepFromBackup + setPrecalcValues + resubstituteFPt inside ldso_ba_optimize), k_resubstitute,
-// k_activate (optimizeImmaturePoint), k_tile_image / k_intensity_image (image staging at load),
-// k_export_newest + k_frame_th (sharded threshold exchange), k_pack_out (results to mapped memory).
+// k_activate (optimizeImmaturePoint), k_tile_image / k_intensity_image (image staging at load and
+// at a host put into the frame store), k_ingest_intensity / k_ingest_texels (device buffer -> frame
+// store slot), k_export_newest + k_frame_th (sharded threshold exchange), k_pack_out (results to mapped memory).
 //
 // The per-residual arithmetic of k_linearize is compiled with contraction off and follows the
 // reference's statement order, so states, energies, JpJdF and the per-point sums are
@@ -4193,6 +4194,53 @@ __global__ void k_tile_image(const float *__restrict__ src, float4 *dst, int w, 
     dst[(((y >> 2) * tpr2 + (x >> 1)) << 3) + ((y & 3) << 1) + (x & 1)] = v;
 }
 
+// Frame store ingest from device memory (ldso_ba_frame_put_device / _tracker).  Both kernels write
+// the whole slot, the padding (x >= w, y >= h) as zero, exactly as the two kernels above leave it.
+// Layout 3: thread per (x, 4-row band): four row-coalesced 4-byte loads from the intensity plane and
+// the band's 16 bytes of column x in one store (float4 index band * wp + x: a wavefront writes 1 KiB
+// per instruction).  No gradient check: the caller's contract is that the frame's gradients are
+// makeImages'.
+__global__ __launch_bounds__(256) void k_ingest_intensity(const float *__restrict__ src, float4 *dst, int w, int h, int wp,
+                                                           int hp) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= wp * (hp >> 2)) return;
+    const int x = i % wp, y0 = (i / wp) << 2;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (x < w)
+        for (int r = 0; r < 4; r++)
+            if (y0 + r < h) v[r] = src[(size_t)(y0 + r) * w + x];
+    dst[i] = make_float4(v[0], v[1], v[2], v[3]);
+}
+// Layout 1: thread per destination texel of the 2x4 tiles (consecutive threads, consecutive
+// texels): [I, dx, dy, absSquaredGrad] -> [I, dx, dy, 0]
+__global__ __launch_bounds__(256) void k_ingest_texels(const float4 *__restrict__ src, float4 *dst, int w, int h,
+                                                        int tpr2, int hp) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= tpr2 * 2 * hp) return;
+    const int tile = i >> 3, x = ((tile % tpr2) << 1) + (i & 1), y = ((tile / tpr2) << 2) + ((i >> 1) & 3);
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (x < w && y < h) {
+        v = src[(size_t)y * w + x];
+        v.w = 0.f;
+    }
+    dst[i] = v;
+}
+// ldso_ba_frame_get: a slot back to row-major planes, intensity [h*w] and (layout 1) grad [h*w][2]
+__global__ __launch_bounds__(256) void k_slot_unpack(const float4 *__restrict__ slot, int mode, float *inten, float *grad,
+                                                      int w, int h, int tpr) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= w * h) return;
+    const int x = i % w, y = i / w;
+    if (mode == 3) {
+        inten[i] = reinterpret_cast<const float *>(slot)[band_offset(x, y, (unsigned)tpr * 8u * 16u) >> 2];
+    } else {
+        const float4 v = slot[(((y >> 2) * tpr + (x >> 1)) << 3) + ((y & 3) << 1) + (x & 1)];
+        inten[i] = v.x;
+        grad[2 * (size_t)i] = v.y;
+        grad[2 * (size_t)i + 1] = v.z;
+    }
+}
+
 template <bool kMarg>
 void launch_linearize(int img_mode, int nb, hipStream_t st, const LinParams &L, hipEvent_t ev_start = nullptr,
                       hipEvent_t ev_stop = nullptr) {
@@ -4343,6 +4391,24 @@ struct ldso_ba_ctx {
     int top_chunk = 0;  // residuals per k_linearize wave (0 = automatic); LDSO_BA_TUNE_TOP_CHUNK
     int solve_exact = 0;  // LDSO_BA_TUNE_SOLVE_EXACT: 1 = the pivoted k_solve_reg / k_solve (bit-identical to the host)
     int img_mode = 3;   // 3 intensity only (band_offset), 1 [I, dx, dy, 0] 2x4 tiles (LDSO_BA_TUNE_TILED_IMAGES)
+    // Frame store (ldso_ba_frames_reserve ...): fs_cap slots of fs_stride float4 in layout fs_mode.
+    // A slot's content is named by the sequence number of the put that wrote it (fs_seq, 0 = free);
+    // img_tag[position of d_img] is the sequence number of the slot content copied there (0 = not
+    // from the store), so ldso_ba_load_frames copies only positions whose tag differs.
+    DevBuf<float4> d_store;
+    int fs_cap = 0, fs_w = 0, fs_h = 0, fs_mode = 0, fs_tpr = 0, fs_hp = 0;
+    long long fs_stride = 0;
+    std::vector<int64_t> fs_id;
+    std::vector<unsigned long long> fs_seq, img_tag;
+    unsigned long long fs_next_seq = 1;
+    int legacy_img_mode = -1;  // ldso_ba_load's layout while a load_frames holds img_mode at the store's (-1: none held)
+    hipEvent_t fs_ev_prod = nullptr, fs_ev_cons = nullptr;  // producer -> ingest, ingest -> producer's next write
+    // image staging, allocated once and grown only: device float3 frame + mismatch flag, pinned host frame
+    DevBuf<float> d_img_stage;
+    DevBuf<int> d_img_flag;
+    char *pin_img = nullptr;
+    size_t pin_img_n = 0;
+    int64_t xfer[4] = {0, 0, 0, 0};  // ldso_ba_transfer_stats
     std::vector<PendingEv> pending;
     std::vector<hipEvent_t> ev_pool;
     double kms[kNumKernels] = {0};
@@ -4545,14 +4611,21 @@ void image_geometry(ldso_ba_ctx *c) {
     }
 }
 
-int stage_images(ldso_ba_ctx *c, const ldso_ba_window *ws, int n_windows, int *mismatch) {
-    float *stage = nullptr;
-    int *flag = nullptr;
-    HIP_TRY(hipMalloc(&stage, (size_t)c->npix * 3 * sizeof(float)));
-    if (hipMalloc(&flag, sizeof(int)) != hipSuccess) {
-        (void)hipFree(stage);
-        return fail(-3, "hipMalloc failed");
+// the context's device staging of one float3 frame and the gradient-mismatch flag (grow-only)
+int image_staging(ldso_ba_ctx *c, size_t npix) {
+    if (c->d_img_stage.n < npix * 3 || !c->d_img_stage.p) {
+        int rc = c->d_img_stage.alloc(npix * 3);
+        if (rc) return rc;
+        c->xfer[2]++;
     }
+    return c->d_img_flag.ensure(1);
+}
+
+int stage_images(ldso_ba_ctx *c, const ldso_ba_window *ws, int n_windows, int *mismatch) {
+    int rc = image_staging(c, (size_t)c->npix);
+    if (rc) return rc;
+    float *stage = c->d_img_stage.p;
+    int *flag = c->d_img_flag.p;
     hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), c->stream);
     int fb = 0;
     for (int w = 0; w < n_windows && e == hipSuccess; w++)
@@ -4560,6 +4633,8 @@ int stage_images(ldso_ba_ctx *c, const ldso_ba_window *ws, int n_windows, int *m
             e = hipMemcpyAsync(stage, ws[w].dI + (size_t)f * c->npix * 3, (size_t)c->npix * 3 * sizeof(float),
                                hipMemcpyHostToDevice, c->stream);
             if (e != hipSuccess) break;
+            c->xfer[0] += (int64_t)c->npix * 3 * sizeof(float);
+            c->xfer[3]++;
             float4 *dst = c->d_img.p + (size_t)fb * c->frame_stride;
             if (c->img_mode == 3) {
                 const long long n = (long long)c->tiles_per_row * 8 * c->padded_h;
@@ -4573,8 +4648,6 @@ int stage_images(ldso_ba_ctx *c, const ldso_ba_window *ws, int n_windows, int *m
         }
     if (e == hipSuccess) e = hipMemcpyAsync(mismatch, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(stage);
-    (void)hipFree(flag);
     if (e != hipSuccess) return fail(-2, std::string("image staging: ") + hipGetErrorString(e));
     return 0;
 }
@@ -4939,6 +5012,9 @@ void ldso_ba_destroy(ldso_ba_ctx *c) {
     if (c->pin_map) (void)hipHostFree(c->pin_map);
     if (c->pin_in) (void)hipHostFree(c->pin_in);
     if (c->pin_in_ev) (void)hipEventDestroy(c->pin_in_ev);
+    if (c->pin_img) (void)hipHostFree(c->pin_img);
+    if (c->fs_ev_prod) (void)hipEventDestroy(c->fs_ev_prod);
+    if (c->fs_ev_cons) (void)hipEventDestroy(c->fs_ev_cons);
     if (c->comm) (void)ncclCommDestroy(c->comm);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -4973,16 +5049,43 @@ struct LoadList {
     }
 };
 
+// slot of a resident frame id, or -1
+int store_find(const ldso_ba_ctx *c, int64_t id) {
+    for (int s = 0; s < c->fs_cap; s++)
+        if (c->fs_seq[s] && c->fs_id[s] == id) return s;
+    return -1;
+}
+
 // parent != nullptr: a marginalisation context over `ws[0]` whose frames are the parent's window
 // parent_win (images borrowed, not uploaded; priorF scaled by setting_idepthFixPriorMargFac)
+// frame_ids != nullptr (ldso_ba_load_frames): the windows' frames are resident in the frame store
+// under these ids, [sum N]; the windows' dI is not read
 int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32_t shard_rank, int32_t shard_count,
-              const ldso_ba_ctx *parent, int parent_win) {
+              const ldso_ba_ctx *parent, int parent_win, const int64_t *frame_ids = nullptr) {
     if (!c || n_windows < 1 || !ws) return fail(-1, "bad arguments");
     if (shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return fail(-1, "bad shard");
-    c->th_host_valid = false;
+    if (frame_ids && c->fs_cap == 0) return fail(LDSO_BA_ERR_FRAME_STORE, "no frame store: call ldso_ba_frames_reserve first");
     Layout L;
-    int rc = build_layout(ws, n_windows, shard_rank, shard_count, c->item_order, c->top_chunk, parent != nullptr, L);
+    int rc = build_layout(ws, n_windows, shard_rank, shard_count, c->item_order, c->top_chunk, parent != nullptr, L,
+                          frame_ids != nullptr);
     if (rc) return rc;
+    // every frame must be resident before anything of the loaded state changes
+    std::vector<int> fslot;
+    if (frame_ids) {
+        size_t k = 0;
+        for (int w = 0; w < n_windows; w++) {
+            if (ws[w].width != c->fs_w || ws[w].height != c->fs_h)
+                return fail(LDSO_BA_ERR_FRAME_STORE, "window size differs from the frame store's");
+            for (int f = 0; f < ws[w].n_frames; f++, k++) {
+                const int s = store_find(c, frame_ids[k]);
+                if (s < 0)
+                    return fail(LDSO_BA_ERR_FRAME_STORE,
+                                "frame id " + std::to_string((long long)frame_ids[k]) + " is not resident in the frame store");
+                fslot.push_back(s);
+            }
+        }
+    }
+    c->th_host_valid = false;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->n_win = n_windows;
@@ -5000,6 +5103,17 @@ int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32
         c->frame_stride = parent->frame_stride;
         c->img_ext = parent->d_img.p + (size_t)parent->wd[parent_win].frame_base * parent->frame_stride;
     } else {
+        // ldso_ba_load keeps the layout it had (the tuning key, or its own fallback) across loads
+        // from the store, which run in the store's layout
+        if (frame_ids) {
+            if (c->img_mode != c->fs_mode) {
+                if (c->legacy_img_mode < 0) c->legacy_img_mode = c->img_mode;
+                c->img_mode = c->fs_mode;
+            }
+        } else if (c->legacy_img_mode >= 0) {
+            c->img_mode = c->legacy_img_mode;
+            c->legacy_img_mode = -1;
+        }
         image_geometry(c);
     }
     c->wh = std::move(L.wh);
@@ -5027,8 +5141,15 @@ int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32
     const std::vector<float> neg(R, -1.0f);  // rs_energy_wo: nothing evaluated yet
     LoadList A{c};
     A.put(c->d_wins, L.wd);
-    if (c->marg) c->d_img.release();
-    else A.alloc(c->d_img, (size_t)c->n_frames * c->frame_stride);
+    const size_t img_n = (size_t)c->n_frames * c->frame_stride;
+    if (c->marg) {
+        c->d_img.release();
+        c->img_tag.clear();
+    } else if (!frame_ids || !c->d_img.p || c->d_img.n < img_n) {
+        A.alloc(c->d_img, img_n);  // a new array (and ldso_ba_load's own images) invalidates the tags
+        c->xfer[2]++;
+        c->img_tag.clear();
+    }
     if (c->marg) A.alloc(c->d_adhtd, (size_t)c->n_pairs * 8);
     A.put(c->d_precalc, L.precalc);
     A.put(c->d_frame_th, L.frame_th);
@@ -5084,7 +5205,21 @@ int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32
     // images: per frame through a float3 staging buffer, repacked on the device; the
     // intensity-only layout falls back to 2x4 float4 tiles if the caller's gradients are not
     // makeImages' (then recomputing them would not be exact)
-    if (!c->marg) {
+    if (frame_ids) {
+        // store slot -> window position, device to device on the context stream, where the
+        // position does not hold that slot's content already
+        c->img_tag.resize((size_t)c->n_frames, 0ull);
+        const size_t bytes = (size_t)c->frame_stride * sizeof(float4);
+        for (int p = 0; p < c->n_frames; p++) {
+            const unsigned long long seq = c->fs_seq[fslot[p]];
+            if (c->img_tag[p] == seq) continue;
+            c->img_tag[p] = 0;
+            HIP_TRY(hipMemcpyAsync(c->d_img.p + (size_t)p * c->frame_stride, c->d_store.p + (size_t)fslot[p] * c->fs_stride,
+                                   bytes, hipMemcpyDeviceToDevice, c->stream));
+            c->img_tag[p] = seq;
+            c->xfer[1] += (int64_t)bytes;
+        }
+    } else if (!c->marg) {
         int mismatch = 0;
         rc = stage_images(c, ws, n_windows, &mismatch);
         if (rc) return rc;
@@ -5092,6 +5227,7 @@ int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32
             c->img_mode = 1;
             image_geometry(c);
             rc = c->d_img.alloc((size_t)c->n_frames * c->frame_stride);
+            c->xfer[2]++;
             if (rc) return rc;
             rc = stage_images(c, ws, n_windows, &mismatch);
             if (rc) return rc;
@@ -5105,6 +5241,60 @@ int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32
         rc = upload_priors(c, w);
         if (rc) return rc;
     }
+    return 0;
+}
+
+// the layout a store reserved now takes: LDSO_BA_TUNE_TILED_IMAGES (or ldso_ba_load's fallback), which
+// legacy_img_mode holds while a load from the store has img_mode
+inline int preferred_img_mode(const ldso_ba_ctx *c) { return c->legacy_img_mode >= 0 ? c->legacy_img_mode : c->img_mode; }
+
+// the slot a put of `id` writes: the id's own if it is resident, else a free one
+int store_slot_for(ldso_ba_ctx *c, int64_t id, int *slot) {
+    if (c->fs_cap == 0) return fail(LDSO_BA_ERR_FRAME_STORE, "no frame store: call ldso_ba_frames_reserve first");
+    int s = store_find(c, id);
+    for (int k = 0; s < 0 && k < c->fs_cap; k++)
+        if (!c->fs_seq[k]) s = k;
+    if (s < 0)
+        return fail(LDSO_BA_ERR_FRAME_STORE, "frame store full (" + std::to_string(c->fs_cap) +
+                                                 " slots): drop a frame before putting id " + std::to_string((long long)id));
+    *slot = s;
+    return 0;
+}
+void store_commit(ldso_ba_ctx *c, int slot, int64_t id) {
+    c->fs_id[slot] = id;
+    c->fs_seq[slot] = c->fs_next_seq++;
+    c->xfer[3]++;
+}
+
+// Device -> slot on the context stream, ordered by events and never by the host: the ingest waits for
+// what the producer's stream holds now (fs_ev_prod), and whatever that stream is given later -- the
+// producer's next overwrite of its buffers -- waits for the ingest (fs_ev_cons).  The slot itself is
+// only ever read and written on the context stream, so stream order keeps the write behind any load
+// still copying out of it.
+int store_ingest_device(ldso_ba_ctx *c, int64_t id, const float *inten, const void *texels, hipStream_t prod) {
+    int slot = -1;
+    int rc = store_slot_for(c, id, &slot);
+    if (rc) return rc;
+    if (c->fs_mode == 1 && !texels)
+        return fail(-1, "image layout 1 stores [I, dx, dy]: the device source must give the texels");
+    if (c->fs_mode == 3 && !inten)
+        return fail(-1, "image layout 3 stores intensities: the device source must give the intensity plane");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipEventRecord(c->fs_ev_prod, prod));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->fs_ev_prod, 0));
+    float4 *dst = c->d_store.p + (size_t)slot * c->fs_stride;
+    if (c->fs_mode == 3) {
+        const int wp = c->fs_tpr * 8, n = wp * (c->fs_hp / 4);
+        k_ingest_intensity<<<(n + 255) / 256, 256, 0, c->stream>>>(inten, dst, c->fs_w, c->fs_h, wp, c->fs_hp);
+    } else {
+        k_ingest_texels<<<(int)((c->fs_stride + 255) / 256), 256, 0, c->stream>>>(static_cast<const float4 *>(texels), dst,
+                                                                                 c->fs_w, c->fs_h, c->fs_tpr, c->fs_hp);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->fs_ev_cons, c->stream));
+    HIP_TRY(hipStreamWaitEvent(prod, c->fs_ev_cons, 0));
+    c->xfer[1] += (int64_t)(c->fs_stride * sizeof(float4));
+    store_commit(c, slot, id);
     return 0;
 }
 }  // namespace
@@ -5126,6 +5316,147 @@ int ldso_ba_load_marginalization(ldso_ba_ctx *marg, const ldso_ba_ctx *parent, i
         return fail(-1, "marginalisation window does not match the parent window's frames");
     marg->settings = parent->settings;  // the parent's affine modes shape res_toZeroF and Jab_r
     return load_impl(marg, 1, points, 0, 1, parent, parent_win);
+}
+
+// ---- frame store ----------------------------------------------------------------------------
+int ldso_ba_frames_reserve(ldso_ba_ctx *c, int32_t capacity, int32_t width, int32_t height) {
+    if (!c) return fail(-1, "null ctx");
+    if (capacity < 1 || capacity > 4096) return fail(-1, "frame store capacity must be in [1, 4096]");
+    if (width < 4 || height < 4 || (long long)width * height > (1ll << 26)) return fail(-1, "bad frame size");
+    if (c->marg) return fail(-1, "a marginalisation context borrows its parent's images and has no frame store");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // a load may still be copying out of the old slots
+    c->fs_cap = 0;
+    c->fs_id.clear();
+    c->fs_seq.clear();
+    c->img_tag.clear();
+    const int mode = preferred_img_mode(c);
+    const int hp = (height + 3) / 4 * 4;
+    const int tpr = mode == 3 ? (width + 7) / 8 : (width + 1) / 2;
+    const long long stride = mode == 3 ? (long long)tpr * 8 * hp / 4 : (long long)tpr * 2 * hp;
+    int rc = c->d_store.alloc((size_t)capacity * stride);
+    c->xfer[2]++;
+    if (rc) return rc;
+    const size_t npix = (size_t)width * height;
+    if ((rc = image_staging(c, npix))) return rc;
+    if ((rc = pin_ensure(c->pin_img, c->pin_img_n, npix * 3 * sizeof(float) + 64))) return rc;
+    if (!c->fs_ev_prod) HIP_TRY(hipEventCreateWithFlags(&c->fs_ev_prod, hipEventDisableTiming));
+    if (!c->fs_ev_cons) HIP_TRY(hipEventCreateWithFlags(&c->fs_ev_cons, hipEventDisableTiming));
+    c->fs_w = width;
+    c->fs_h = height;
+    c->fs_mode = mode;
+    c->fs_tpr = tpr;
+    c->fs_hp = hp;
+    c->fs_stride = stride;
+    c->fs_id.assign((size_t)capacity, 0);
+    c->fs_seq.assign((size_t)capacity, 0ull);
+    c->fs_cap = capacity;
+    return 0;
+}
+
+int ldso_ba_frame_put(ldso_ba_ctx *c, int64_t frame_id, const float *dI) {
+    if (!c || !dI) return fail(-1, "null argument");
+    int slot = -1;
+    int rc = store_slot_for(c, frame_id, &slot);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t npix = (size_t)c->fs_w * c->fs_h, bytes = npix * 3 * sizeof(float);
+    if ((rc = image_staging(c, npix))) return rc;
+    if ((rc = pin_ensure(c->pin_img, c->pin_img_n, bytes + 64))) return rc;
+    // every use of the pinned frame ends behind a synchronisation, so it is free here
+    std::memcpy(c->pin_img, dI, bytes);
+    int *mismatch = reinterpret_cast<int *>(c->pin_img + bytes);
+    *mismatch = 0;
+    HIP_TRY(hipMemsetAsync(c->d_img_flag.p, 0, sizeof(int), c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_img_stage.p, c->pin_img, bytes, hipMemcpyHostToDevice, c->stream));
+    c->xfer[0] += (int64_t)bytes;
+    float4 *dst = c->d_store.p + (size_t)slot * c->fs_stride;
+    if (c->fs_mode == 3) {
+        const long long n = (long long)c->fs_tpr * 8 * c->fs_hp;
+        k_intensity_image<<<(int)((n + 255) / 256), 256, 0, c->stream>>>(c->d_img_stage.p, reinterpret_cast<float *>(dst),
+                                                                         c->fs_w, c->fs_h, c->fs_tpr, c->fs_hp, c->d_img_flag.p);
+    } else {
+        k_tile_image<<<(int)((c->fs_stride + 255) / 256), 256, 0, c->stream>>>(c->d_img_stage.p, dst, c->fs_w, c->fs_h,
+                                                                              c->fs_tpr, c->fs_hp);
+    }
+    HIP_TRY(hipGetLastError());
+    if (c->fs_mode == 3) HIP_TRY(hipMemcpyAsync(mismatch, c->d_img_flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->fs_mode == 3 && *mismatch) {
+        c->fs_seq[slot] = 0;  // the slot holds intensities whose recomputed gradients are not the caller's
+        return fail(LDSO_BA_ERR_GRADIENT_MISMATCH,
+                    "frame id " + std::to_string((long long)frame_id) +
+                        ": dI's gradients are not makeImages' (FrameHessian.cc:96-101), which image layout 3 recomputes; "
+                        "reserve the frame store in layout 1 (LDSO_BA_TUNE_TILED_IMAGES = 1 before ldso_ba_frames_reserve)");
+    }
+    store_commit(c, slot, frame_id);
+    return 0;
+}
+
+int ldso_ba_frame_put_device(ldso_ba_ctx *c, int64_t frame_id, const float *dev_intensity, const void *dev_texels,
+                             void *producer_stream) {
+    if (!c) return fail(-1, "null ctx");
+    if (!dev_intensity && !dev_texels) return fail(-1, "no device source: give the intensity plane and / or the texels");
+    return store_ingest_device(c, frame_id, dev_intensity, dev_texels, static_cast<hipStream_t>(producer_stream));
+}
+
+int ldso_ba_frame_put_tracker(ldso_ba_ctx *c, int64_t frame_id, const ldso_ct_ctx *tracker) {
+    if (!c || !tracker) return fail(-1, "null argument");
+    if (c->fs_cap == 0) return fail(LDSO_BA_ERR_FRAME_STORE, "no frame store: call ldso_ba_frames_reserve first");
+    ldso_ba::CtFrameView v{};
+    int rc = ldso_ba::ct_frame_view(tracker, &v);
+    if (rc) return rc;
+    if (v.device != c->device) return fail(-1, "tracker and context are on different devices");
+    if (v.width != c->fs_w || v.height != c->fs_h)
+        return fail(LDSO_BA_ERR_FRAME_STORE, "tracker frame is " + std::to_string(v.width) + "x" + std::to_string(v.height) +
+                                                 ", the frame store holds " + std::to_string(c->fs_w) + "x" +
+                                                 std::to_string(c->fs_h));
+    if (!v.have_frame) return fail(-1, "the tracker has no new frame: ldso_ct_set_new_frame not called");
+    return store_ingest_device(c, frame_id, v.intensity, v.texels, static_cast<hipStream_t>(v.stream));
+}
+
+int ldso_ba_frame_drop(ldso_ba_ctx *c, int64_t frame_id) {
+    if (!c) return fail(-1, "null ctx");
+    const int s = store_find(c, frame_id);
+    if (s < 0)
+        return fail(LDSO_BA_ERR_FRAME_STORE, "frame id " + std::to_string((long long)frame_id) + " is not resident in the frame store");
+    c->fs_seq[s] = 0;  // the next put into the slot is ordered behind its readers on the context stream
+    return 0;
+}
+
+int ldso_ba_frame_get(ldso_ba_ctx *c, int64_t frame_id, float *intensity, float *grad) {
+    if (!c || !intensity) return fail(-1, "null argument");
+    const int s = store_find(c, frame_id);
+    if (s < 0)
+        return fail(LDSO_BA_ERR_FRAME_STORE, "frame id " + std::to_string((long long)frame_id) + " is not resident in the frame store");
+    if (grad && c->fs_mode != 1) return fail(-1, "image layout 3 stores no gradients: grad must be NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t npix = (size_t)c->fs_w * c->fs_h;
+    int rc = image_staging(c, npix);
+    if (rc) return rc;
+    if ((rc = pin_ensure(c->pin_img, c->pin_img_n, npix * 3 * sizeof(float) + 64))) return rc;
+    float *d_i = c->d_img_stage.p, *d_g = c->d_img_stage.p + npix;
+    k_slot_unpack<<<(int)((npix + 255) / 256), 256, 0, c->stream>>>(c->d_store.p + (size_t)s * c->fs_stride, c->fs_mode, d_i,
+                                                                    d_g, c->fs_w, c->fs_h, c->fs_tpr);
+    HIP_TRY(hipGetLastError());
+    const size_t n = npix * (grad ? 3 : 1);
+    HIP_TRY(hipMemcpyAsync(c->pin_img, d_i, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::memcpy(intensity, c->pin_img, npix * sizeof(float));
+    if (grad) std::memcpy(grad, c->pin_img + npix * sizeof(float), 2 * npix * sizeof(float));
+    return 0;
+}
+
+int ldso_ba_load_frames(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, const int64_t *frame_ids,
+                        int32_t shard_rank, int32_t shard_count) {
+    if (!c || !ws || !frame_ids) return fail(-1, "bad arguments");
+    return load_impl(c, n_windows, ws, shard_rank, shard_count, nullptr, 0, frame_ids);
+}
+
+int ldso_ba_transfer_stats(ldso_ba_ctx *c, int64_t out[4]) {
+    if (!c || !out) return fail(-1, "null argument");
+    for (int i = 0; i < 4; i++) out[i] = c->xfer[i];
+    return 0;
 }
 
 int ldso_ba_update(ldso_ba_ctx *c, int32_t win, const ldso_ba_window *w) {
@@ -6464,7 +6795,7 @@ int32_t ldso_ba_num_kernels(void) { return kNumKernels; }
 int ldso_ba_stats(ldso_ba_ctx *c, int64_t *device_bytes, int64_t *n_points, int64_t *n_residuals) {
     if (!c) return fail(-1, "null ctx");
     if (device_bytes)
-        *device_bytes = (int64_t)(c->d_img.bytes() + c->d_precalc.bytes() + c->d_pt_data.bytes() + c->d_rec_a.bytes() + c->d_rec_b.bytes() +
+        *device_bytes = (int64_t)(c->d_img.bytes() + c->d_store.bytes() + c->d_precalc.bytes() + c->d_pt_data.bytes() + c->d_rec_a.bytes() + c->d_rec_b.bytes() +
                                   c->d_top_slab.bytes() + c->d_sc_slab.bytes() + c->d_sys.bytes());
     if (n_points) *n_points = c->P_tot;
     if (n_residuals) *n_residuals = c->R_tot;

@@ -96,6 +96,18 @@ LDSO_HD inline bool gram_inverse_coef7(const double (&G)[7][7], const double (&n
 int set_error(int code, const std::string &msg);
 const char *last_error();
 
+// The coarse tracker's current new frame as the BA frame store ingests it (ldso_ct.hip; the BA
+// translation unit does not see ldso_ct_ctx): level 0 of d_inten / d_dIp, which start the flat
+// pyramid buffers.  texels: float4 [I, dx, dy, absSquaredGrad], row-major.
+struct CtFrameView {
+    const float *intensity;
+    const void *texels;
+    int width, height, device;
+    void *stream;     // hipStream_t every tracker kernel and copy runs on
+    bool have_frame;  // ldso_ct_set_new_frame has run
+};
+int ct_frame_view(const ldso_ct_ctx *ct, CtFrameView *out);
+
 int frame_precalc(int N, const ldso_ba_frame_state *fr, const float calib[4], float *out);
 int set_adjoints(int N, const ldso_ba_frame_state *fr, double *adH, double *adT, double *cPrior);
 int frame_take_data(int N, const ldso_ba_frame_state *fr, float mode_a, float mode_b, double *prior, double *delta,

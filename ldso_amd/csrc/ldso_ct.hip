@@ -715,6 +715,19 @@ struct ldso_ct_ctx {
     long long cnt[kNumCtKernels] = {0};
 };
 
+// the BA frame store's view of the new frame (ldso_ba_frame_put_tracker)
+int ldso_ba::ct_frame_view(const ldso_ct_ctx *c, ldso_ba::CtFrameView *out) {
+    if (!c || !out) return set_error(-1, "null argument");
+    out->intensity = c->d_inten;
+    out->texels = c->d_dIp;
+    out->width = c->pyr.w;
+    out->height = c->pyr.h;
+    out->device = c->device;
+    out->stream = (void *)c->stream;
+    out->have_frame = c->have_frame;
+    return 0;
+}
+
 namespace {
 
 template <typename F>
