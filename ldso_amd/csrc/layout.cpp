@@ -37,6 +37,22 @@ int check_window(const ldso_ba_window &w, bool need_images) {
     return 0;
 }
 
+ImageLayout image_layout(int mode, int width, int height) {
+    ImageLayout l;
+    l.mode = mode;
+    l.width = width;
+    l.height = height;
+    l.padded_h = (height + 3) / 4 * 4;
+    if (mode == 3) {
+        l.tiles_per_row = (width + 7) / 8;
+        l.frame_stride = (long long)l.tiles_per_row * 8 * l.padded_h / 4;
+    } else {
+        l.tiles_per_row = (width + 1) / 2;
+        l.frame_stride = (long long)l.tiles_per_row * 2 * l.padded_h;
+    }
+    return l;
+}
+
 size_t sc_smem_bytes(int KP) {
     return ((size_t)kScPoints * (KP + 4) + (size_t)LDSO_BA_MAX_FRAMES * kPrePitch) * sizeof(float);
 }

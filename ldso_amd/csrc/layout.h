@@ -49,6 +49,22 @@ LDSO_HD inline long long sys_len(int D) { return 2 * (packed_len(D) + D); }
 // doubles of k_stitch's contribution record of one (h, t) pair (its fields: ba_device.h)
 LDSO_HD inline int stage_rec(int N) { return 520 + 64 * (N - 1); }
 
+// One frame as the kernels read it, in the window's image array or in a frame-store slot, padded
+// to whole tiles.  mode 3: intensity only, 8-pixel x 4-row bands (band_offset); mode 1:
+// [I, dx, dy, 0] texels in 2x4 tiles.
+struct ImageLayout {
+    int mode = 3, width = 0, height = 0;
+    int tiles_per_row = 0;       // mode 3: 8-pixel tiles per row; mode 1: 2-texel tiles per row
+    int padded_h = 0;            // height rounded up to whole 4-row tiles
+    long long frame_stride = 0;  // float4 units per frame
+    size_t npix() const { return (size_t)width * height; }
+    size_t slot_bytes() const { return (size_t)frame_stride * 16; }
+    // elements the repack of a staged float3 frame writes, one thread each: mode 3 the padded
+    // intensities (k_intensity_image), mode 1 the padded texels (k_tile_image)
+    long long repack_elems() const { return mode == 3 ? (long long)tiles_per_row * 8 * padded_h : frame_stride; }
+};
+ImageLayout image_layout(int mode, int width, int height);
+
 constexpr int kScPoints = 64;  // points per k_point_sc block (large loads; small ones take 16)
 constexpr int kPrePitch = 12;  // floats of staged precalc (R0, t0) per target in k_point_sc's LDS
 // k_point_sc dynamic LDS of a window whose padded Schur block is KP wide

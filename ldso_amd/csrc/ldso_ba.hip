@@ -4294,9 +4294,103 @@ struct DevBuf {
     size_t bytes() const { return n * sizeof(T); }
 };
 
+// Grow-only pinned host staging of n elements (the address is kept while it fits), freed with the
+// context.  With hipHostMallocMapped in kFlags the device reads or writes it directly through dev.
+template <typename T, unsigned kFlags = hipHostMallocDefault>
+struct PinBuf {
+    T *p = nullptr, *dev = nullptr;
+    size_t n = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+    ~PinBuf() {
+        if (p) (void)hipHostFree(p);
+    }
+    // the caller has made sure that nothing still uses the old buffer
+    int ensure(size_t count, size_t min_bytes = 64) {
+        if (p && n >= count) return 0;
+        if (p) (void)hipHostFree(p);
+        p = dev = nullptr;
+        n = 0;
+        const size_t bytes = std::max(count * sizeof(T), min_bytes);
+        HIP_TRY(hipHostMalloc((void **)&p, bytes, kFlags));
+        if (kFlags & hipHostMallocMapped) {
+            void *d = nullptr;
+            HIP_TRY(hipHostGetDevicePointer(&d, p, 0));
+            dev = static_cast<T *>(d);
+        }
+        n = bytes / sizeof(T);
+        return 0;
+    }
+};
+// coherent host memory the device addresses: its stores are visible to the host once the stream has
+// synchronised, and the host's stores to a launch that follows them
+using PinMapped = PinBuf<char, hipHostMallocCoherent | hipHostMallocMapped>;
+
+// an event created at first use and destroyed with its owner
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() {
+        if (e) (void)hipEventDestroy(e);
+    }
+    int ensure(unsigned flags) {
+        if (!e) HIP_TRY(hipEventCreateWithFlags(&e, flags));
+        return 0;
+    }
+};
+
 struct PendingEv {
     int slot;
     hipEvent_t a, b;
+};
+// the events of the timed launches, created ahead of them and reused (drain_events returns them)
+struct EventPool {
+    std::vector<hipEvent_t> free;
+    EventPool() = default;
+    EventPool(const EventPool &) = delete;
+    EventPool &operator=(const EventPool &) = delete;
+    ~EventPool() {
+        for (hipEvent_t e : free) (void)hipEventDestroy(e);
+    }
+};
+
+// Frame store (ldso_ba_frames_reserve ...): cap slots of one ImageLayout.  A slot's content is named
+// by the sequence number of the put that wrote it (seq, 0 = free).
+struct FrameStore {
+    DevBuf<float4> d_store;
+    ImageLayout lay;
+    int cap = 0;
+    std::vector<int64_t> id;
+    std::vector<unsigned long long> seq;
+    unsigned long long next_seq = 1;
+    Event ev_prod, ev_cons;  // producer -> ingest, ingest -> producer's next write
+    float4 *slot(int s) const { return d_store.p + (size_t)s * lay.frame_stride; }
+    // slot of a resident frame id, or -1
+    int find(int64_t frame_id) const {
+        for (int s = 0; s < cap; s++)
+            if (seq[s] && id[s] == frame_id) return s;
+        return -1;
+    }
+    // the slot a put of `frame_id` writes: the id's own if it is resident, else a free one
+    int slot_for(int64_t frame_id, int *out) const {
+        if (cap == 0) return fail(LDSO_BA_ERR_FRAME_STORE, "no frame store: call ldso_ba_frames_reserve first");
+        int s = find(frame_id);
+        for (int k = 0; s < 0 && k < cap; k++)
+            if (!seq[k]) s = k;
+        if (s < 0)
+            return fail(LDSO_BA_ERR_FRAME_STORE, "frame store full (" + std::to_string(cap) +
+                                                     " slots): drop a frame before putting id " +
+                                                     std::to_string((long long)frame_id));
+        *out = s;
+        return 0;
+    }
+    void commit(int s, int64_t frame_id) {
+        id[s] = frame_id;
+        seq[s] = next_seq++;
+    }
 };
 
 }  // namespace
@@ -4317,22 +4411,38 @@ struct ldso_ba_ctx {
         hipGraphExec_t exec = nullptr;
         unsigned long long gen = 0;
         std::vector<unsigned long long> key;
+        Graph() = default;
+        Graph(const Graph &) = delete;
+        Graph &operator=(const Graph &) = delete;
+        ~Graph() { reset(); }
+        void reset() {
+            if (exec) (void)hipGraphExecDestroy(exec);
+            exec = nullptr;
+        }
     };
     Graph opt_graph[2], it_graph[2];  // ldso_ba_optimize's whole call (without / with nullspaces)
     bool opt_warm = false;            // an optimize call ran directly on this context
     int item_order = 0;  // k_linearize chunk order: 0 target-major, 1 host-major, 2 target-major banded
     // the reference's settings this context runs with (ldso_ba_set_settings; always checked)
     ldso_ba_opt_settings settings = LDSO_BA_OPT_SETTINGS_INIT;
-    int n_win = 0, width = 0, height = 0, npix = 0;
+    int n_win = 0;
     std::vector<WinHost> wh;
     std::vector<WinDev> wd;
     int n_top_items = 0, n_sc_items = 0, n_pairs = 0, n_frames = 0, P_tot = 0, R_tot = 0, max_frames = 0;
     DevBuf<WinDev> d_wins;
+    // the frames the kernels read: n_frames x img.frame_stride float4.  img is the layout of what is
+    // loaded; img_mode_pref the one ldso_ba_load and ldso_ba_frames_reserve take
+    // (LDSO_BA_TUNE_TILED_IMAGES, or ldso_ba_load's fallback to 1), which a load from the store, in
+    // the store's layout, leaves alone.  img_tag[position of d_img] is the sequence number of the
+    // store slot content copied there (0 = not from the store), so ldso_ba_load_frames copies only
+    // positions whose tag differs.
     DevBuf<float4> d_img;
+    ImageLayout img;
+    int img_mode_pref = 3;
+    std::vector<unsigned long long> img_tag;
+    FrameStore store;
     DevBuf<ldso_ct_immature> d_act_in;  // point activation staging (ldso_ba_activate_points)
     DevBuf<ldso_ba_activation> d_act_out;
-    int tiles_per_row = 0, padded_h = 0;
-    long long frame_stride = 0;
     DevBuf<float> d_precalc, d_frame_th, d_pt_data, d_pt_out, d_pt_step;
     DevBuf<double> d_adH, d_adT;
     DevBuf<int> d_rs_slot, d_pt_nres, d_pair_win, d_frame_win, d_pt_host;
@@ -4390,27 +4500,13 @@ struct ldso_ba_ctx {
     unsigned timing_mask = ~0u;  // kernel slots bracketed by events when timing is on
     int top_chunk = 0;  // residuals per k_linearize wave (0 = automatic); LDSO_BA_TUNE_TOP_CHUNK
     int solve_exact = 0;  // LDSO_BA_TUNE_SOLVE_EXACT: 1 = the pivoted k_solve_reg / k_solve (bit-identical to the host)
-    int img_mode = 3;   // 3 intensity only (band_offset), 1 [I, dx, dy, 0] 2x4 tiles (LDSO_BA_TUNE_TILED_IMAGES)
-    // Frame store (ldso_ba_frames_reserve ...): fs_cap slots of fs_stride float4 in layout fs_mode.
-    // A slot's content is named by the sequence number of the put that wrote it (fs_seq, 0 = free);
-    // img_tag[position of d_img] is the sequence number of the slot content copied there (0 = not
-    // from the store), so ldso_ba_load_frames copies only positions whose tag differs.
-    DevBuf<float4> d_store;
-    int fs_cap = 0, fs_w = 0, fs_h = 0, fs_mode = 0, fs_tpr = 0, fs_hp = 0;
-    long long fs_stride = 0;
-    std::vector<int64_t> fs_id;
-    std::vector<unsigned long long> fs_seq, img_tag;
-    unsigned long long fs_next_seq = 1;
-    int legacy_img_mode = -1;  // ldso_ba_load's layout while a load_frames holds img_mode at the store's (-1: none held)
-    hipEvent_t fs_ev_prod = nullptr, fs_ev_cons = nullptr;  // producer -> ingest, ingest -> producer's next write
     // image staging, allocated once and grown only: device float3 frame + mismatch flag, pinned host frame
     DevBuf<float> d_img_stage;
     DevBuf<int> d_img_flag;
-    char *pin_img = nullptr;
-    size_t pin_img_n = 0;
+    PinBuf<char> pin_img;
     int64_t xfer[4] = {0, 0, 0, 0};  // ldso_ba_transfer_stats
     std::vector<PendingEv> pending;
-    std::vector<hipEvent_t> ev_pool;
+    EventPool ev_pool;
     double kms[kNumKernels] = {0};
     long long kcount[kNumKernels] = {0};
     std::vector<double> sys_host;  // last downloaded packed systems (per window, see sys_valid)
@@ -4418,18 +4514,14 @@ struct ldso_ba_ctx {
     bool sys_host_valid = false;   // false => every window's host copy is stale
     // pinned staging for the per-iteration host round trips (system download, xAd upload,
     // point-step download): async copies with one synchronisation each
-    double *pin_sys = nullptr;
-    float *pin_xad = nullptr, *pin_step = nullptr;
-    size_t pin_sys_n = 0, pin_step_n = 0;
+    PinBuf<double> pin_sys;
+    PinBuf<float> pin_xad, pin_step;
     // pinned staging for the results of ldso_ba_iterate / ldso_ba_optimize: every download of
     // one call lands here, behind a single synchronisation
-    char *pin_out = nullptr;
-    size_t pin_out_n = 0;
-    char *pin_map = nullptr, *pin_map_dev = nullptr;  // fine-grained pinned results buffer, written by k_pack_out
-    size_t pin_map_n = 0;
-    char *pin_in = nullptr, *pin_in_dev = nullptr;  // mapped staging of small uploads, read by k_pack_out
-    size_t pin_in_n = 0;
-    hipEvent_t pin_in_ev = nullptr;  // the last launch reading pin_in
+    PinBuf<char> pin_out;
+    PinMapped pin_map;  // fine-grained pinned results buffer, written by k_pack_out
+    PinMapped pin_in;   // mapped staging of small uploads, read by k_pack_out
+    Event pin_in_ev;    // the last launch reading pin_in
     bool pin_in_busy = false;
     std::vector<double> energy_host;
     bool energy_valid = false;
@@ -4453,36 +4545,18 @@ inline int aff_fix_bits(const ldso_ba_ctx *c) {
     return (c->settings.affine_opt_mode_a < 0 ? 1 : 0) | (c->settings.affine_opt_mode_b < 0 ? 2 : 0);
 }
 
-// grow-only pinned host staging (the address is kept while it fits)
-int pin_ensure(char *&p, size_t &cap, size_t bytes) {
-    bytes = std::max<size_t>(bytes, 64);
-    if (p && cap >= bytes) return 0;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    HIP_TRY(hipHostMalloc((void **)&p, bytes, hipHostMallocDefault));
-    cap = bytes;
-    return 0;
+// the results buffer the device writes directly, so a call's results come back in one launch
+// instead of one blit per array; a launch of an earlier call may still be writing the old one
+int pin_map_ensure(ldso_ba_ctx *c, size_t bytes) {
+    if (c->pin_map.p && c->pin_map.n < bytes) HIP_TRY(hipStreamSynchronize(c->stream));
+    return c->pin_map.ensure(bytes);
 }
 
-// the results buffer the device writes directly (coherent host memory: k_pack_out's stores are
-// visible to the host once the stream has synchronised), so a call's results come back in one
-// launch instead of one blit per array
-int pin_map_ensure(ldso_ba_ctx *c, size_t bytes) {
-    bytes = std::max<size_t>(bytes, 64);
-    if (c->pin_map && c->pin_map_n >= bytes) return 0;
-    if (c->pin_map) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        (void)hipHostFree(c->pin_map);
-    }
-    c->pin_map = c->pin_map_dev = nullptr;
-    c->pin_map_n = 0;
-    HIP_TRY(hipHostMalloc((void **)&c->pin_map, bytes, hipHostMallocCoherent | hipHostMallocMapped));
-    void *d = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&d, c->pin_map, 0));
-    c->pin_map_dev = static_cast<char *>(d);
-    c->pin_map_n = bytes;
-    return 0;
+// one more array (whole 4-byte words) for k_pack_out to copy
+inline void pack_seg(PackOut &K, const void *src, void *dst, size_t bytes) {
+    K.src[K.n_seg] = static_cast<const unsigned *>(src);
+    K.dst[K.n_seg] = static_cast<unsigned *>(dst);
+    K.words[K.n_seg++] = (int)(bytes / 4);
 }
 
 // Small host -> device uploads of one call gathered into the mapped staging buffer and written
@@ -4504,28 +4578,17 @@ int InBatch::flush(ldso_ba_ctx *c) {
     size_t total = 0;
     for (const Item &it : items) total += (it.bytes + 15) & ~(size_t)15;
     if (c->pin_in_busy) {  // the previous launch must have read the staging buffer
-        HIP_TRY(hipEventSynchronize(c->pin_in_ev));
+        HIP_TRY(hipEventSynchronize(c->pin_in_ev.e));
         c->pin_in_busy = false;
     }
-    if (!c->pin_in || c->pin_in_n < total) {
-        if (c->pin_in) (void)hipHostFree(c->pin_in);
-        c->pin_in = c->pin_in_dev = nullptr;
-        c->pin_in_n = 0;
-        HIP_TRY(hipHostMalloc((void **)&c->pin_in, std::max<size_t>(total, 4096), hipHostMallocCoherent | hipHostMallocMapped));
-        void *d = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(&d, c->pin_in, 0));
-        c->pin_in_dev = static_cast<char *>(d);
-        c->pin_in_n = std::max<size_t>(total, 4096);
-    }
-    if (!c->pin_in_ev) HIP_TRY(hipEventCreateWithFlags(&c->pin_in_ev, hipEventDisableTiming));
+    int rc = c->pin_in.ensure(total, 4096);
+    if (rc || (rc = c->pin_in_ev.ensure(hipEventDisableTiming))) return rc;
     size_t off = 0;
     PackOut K{};
     for (size_t k = 0; k < items.size(); k++) {
         const Item &it = items[k];
-        std::memcpy(c->pin_in + off, it.src, it.bytes);
-        K.src[K.n_seg] = reinterpret_cast<const unsigned *>(c->pin_in_dev + off);
-        K.dst[K.n_seg] = static_cast<unsigned *>(it.dst);
-        K.words[K.n_seg++] = (int)(it.bytes / 4);
+        std::memcpy(c->pin_in.p + off, it.src, it.bytes);
+        pack_seg(K, c->pin_in.dev + off, it.dst, it.bytes);
         off += (it.bytes + 15) & ~(size_t)15;
         if (K.n_seg == kPackSegs || k + 1 == items.size()) {
             k_pack_out<<<std::min(64, (int)(total / 1024) + 1), 256, 0, c->stream>>>(K);
@@ -4533,16 +4596,16 @@ int InBatch::flush(ldso_ba_ctx *c) {
             K = PackOut{};
         }
     }
-    HIP_TRY(hipEventRecord(c->pin_in_ev, c->stream));
+    HIP_TRY(hipEventRecord(c->pin_in_ev.e, c->stream));
     c->pin_in_busy = true;
     items.clear();
     return 0;
 }
 
 hipEvent_t get_event(ldso_ba_ctx *c) {
-    if (!c->ev_pool.empty()) {
-        hipEvent_t e = c->ev_pool.back();
-        c->ev_pool.pop_back();
+    if (!c->ev_pool.free.empty()) {
+        hipEvent_t e = c->ev_pool.free.back();
+        c->ev_pool.free.pop_back();
         return e;
     }
     hipEvent_t e;
@@ -4559,8 +4622,8 @@ void drain_events(ldso_ba_ctx *c) {
         (void)hipEventElapsedTime(&ms, pe.a, pe.b);
         c->kms[pe.slot] += ms;
         c->kcount[pe.slot] += 1;
-        c->ev_pool.push_back(pe.a);
-        c->ev_pool.push_back(pe.b);
+        c->ev_pool.free.push_back(pe.a);
+        c->ev_pool.free.push_back(pe.b);
     }
     c->pending.clear();
 }
@@ -4599,16 +4662,16 @@ int timed_launch(ldso_ba_ctx *c, int slot, hipStream_t st, F &&launch) {
     return timed_launch_events(c, slot, st, [&](hipEvent_t, hipEvent_t) { launch(); });
 }
 
-// frame geometry of the image layout (all strides in float4 units)
-void image_geometry(ldso_ba_ctx *c) {
-    c->padded_h = (c->height + 3) / 4 * 4;
-    if (c->img_mode == 3) {
-        c->tiles_per_row = (c->width + 7) / 8;
-        c->frame_stride = (long long)c->tiles_per_row * 8 * c->padded_h / 4;
-    } else {
-        c->tiles_per_row = (c->width + 1) / 2;
-        c->frame_stride = (long long)c->tiles_per_row * 2 * c->padded_h;
-    }
+// One staged float3 frame repacked into a slot of layout l (of the window's image array or of the
+// frame store).  Layout 3 keeps the intensities and raises *flag if the frame's gradients are not
+// the ones it will recompute.
+void launch_repack(const ImageLayout &l, const float *stage, float4 *dst, int *flag, hipStream_t st) {
+    const int nb = (int)((l.repack_elems() + 255) / 256);
+    if (l.mode == 3)
+        k_intensity_image<<<nb, 256, 0, st>>>(stage, reinterpret_cast<float *>(dst), l.width, l.height, l.tiles_per_row,
+                                              l.padded_h, flag);
+    else
+        k_tile_image<<<nb, 256, 0, st>>>(stage, dst, l.width, l.height, l.tiles_per_row, l.padded_h);
 }
 
 // the context's device staging of one float3 frame and the gradient-mismatch flag (grow-only)
@@ -4622,7 +4685,8 @@ int image_staging(ldso_ba_ctx *c, size_t npix) {
 }
 
 int stage_images(ldso_ba_ctx *c, const ldso_ba_window *ws, int n_windows, int *mismatch) {
-    int rc = image_staging(c, (size_t)c->npix);
+    const size_t npix = c->img.npix();
+    int rc = image_staging(c, npix);
     if (rc) return rc;
     float *stage = c->d_img_stage.p;
     int *flag = c->d_img_flag.p;
@@ -4630,20 +4694,12 @@ int stage_images(ldso_ba_ctx *c, const ldso_ba_window *ws, int n_windows, int *m
     int fb = 0;
     for (int w = 0; w < n_windows && e == hipSuccess; w++)
         for (int f = 0; f < ws[w].n_frames && e == hipSuccess; f++, fb++) {
-            e = hipMemcpyAsync(stage, ws[w].dI + (size_t)f * c->npix * 3, (size_t)c->npix * 3 * sizeof(float),
-                               hipMemcpyHostToDevice, c->stream);
+            e = hipMemcpyAsync(stage, ws[w].dI + (size_t)f * npix * 3, npix * 3 * sizeof(float), hipMemcpyHostToDevice,
+                               c->stream);
             if (e != hipSuccess) break;
-            c->xfer[0] += (int64_t)c->npix * 3 * sizeof(float);
+            c->xfer[0] += (int64_t)(npix * 3 * sizeof(float));
             c->xfer[3]++;
-            float4 *dst = c->d_img.p + (size_t)fb * c->frame_stride;
-            if (c->img_mode == 3) {
-                const long long n = (long long)c->tiles_per_row * 8 * c->padded_h;
-                k_intensity_image<<<(int)((n + 255) / 256), 256, 0, c->stream>>>(
-                    stage, reinterpret_cast<float *>(dst), c->width, c->height, c->tiles_per_row, c->padded_h, flag);
-            } else {
-                k_tile_image<<<(int)((c->frame_stride + 255) / 256), 256, 0, c->stream>>>(
-                    stage, dst, c->width, c->height, c->tiles_per_row, c->padded_h);
-            }
+            launch_repack(c->img, stage, c->d_img.p + (size_t)fb * c->img.frame_stride, flag, c->stream);
             e = hipGetLastError();
         }
     if (e == hipSuccess) e = hipMemcpyAsync(mismatch, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream);
@@ -4725,8 +4781,8 @@ LinParams lin_params(const ldso_ba_ctx *c) {
     L.geo_snap = c->d_geo_snap.p;
     L.top_slab = c->d_top_slab.p;
     L.item_energy = c->d_item_energy.p;
-    L.frame_stride = c->frame_stride;
-    L.tiles_per_row = c->tiles_per_row;
+    L.frame_stride = c->img.frame_stride;
+    L.tiles_per_row = c->img.tiles_per_row;
     L.aff_fix = aff_fix_bits(c);
     L.item_base = 0;
     L.n_items = c->n_top_items;
@@ -4999,24 +5055,11 @@ void ldso_ba_destroy(ldso_ba_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto &g : c->opt_graph)
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    for (auto &g : c->it_graph)
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    drain_events(c);
-    for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->pin_sys) (void)hipHostFree(c->pin_sys);
-    if (c->pin_xad) (void)hipHostFree(c->pin_xad);
-    if (c->pin_step) (void)hipHostFree(c->pin_step);
-    if (c->pin_out) (void)hipHostFree(c->pin_out);
-    if (c->pin_map) (void)hipHostFree(c->pin_map);
-    if (c->pin_in) (void)hipHostFree(c->pin_in);
-    if (c->pin_in_ev) (void)hipEventDestroy(c->pin_in_ev);
-    if (c->pin_img) (void)hipHostFree(c->pin_img);
-    if (c->fs_ev_prod) (void)hipEventDestroy(c->fs_ev_prod);
-    if (c->fs_ev_cons) (void)hipEventDestroy(c->fs_ev_cons);
+    drain_events(c);  // the pending events go back to the pool, which destroys them
     if (c->comm) (void)ncclCommDestroy(c->comm);
     if (c->stream) (void)hipStreamDestroy(c->stream);
+    // every member frees what it owns (device and pinned buffers, events, graph execs): the work
+    // that used them has completed, the device is current, and no release needs the stream
     delete c;
 }
 
@@ -5049,13 +5092,6 @@ struct LoadList {
     }
 };
 
-// slot of a resident frame id, or -1
-int store_find(const ldso_ba_ctx *c, int64_t id) {
-    for (int s = 0; s < c->fs_cap; s++)
-        if (c->fs_seq[s] && c->fs_id[s] == id) return s;
-    return -1;
-}
-
 // parent != nullptr: a marginalisation context over `ws[0]` whose frames are the parent's window
 // parent_win (images borrowed, not uploaded; priorF scaled by setting_idepthFixPriorMargFac)
 // frame_ids != nullptr (ldso_ba_load_frames): the windows' frames are resident in the frame store
@@ -5064,7 +5100,8 @@ int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32
               const ldso_ba_ctx *parent, int parent_win, const int64_t *frame_ids = nullptr) {
     if (!c || n_windows < 1 || !ws) return fail(-1, "bad arguments");
     if (shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return fail(-1, "bad shard");
-    if (frame_ids && c->fs_cap == 0) return fail(LDSO_BA_ERR_FRAME_STORE, "no frame store: call ldso_ba_frames_reserve first");
+    const FrameStore &S = c->store;
+    if (frame_ids && S.cap == 0) return fail(LDSO_BA_ERR_FRAME_STORE, "no frame store: call ldso_ba_frames_reserve first");
     Layout L;
     int rc = build_layout(ws, n_windows, shard_rank, shard_count, c->item_order, c->top_chunk, parent != nullptr, L,
                           frame_ids != nullptr);
@@ -5074,10 +5111,10 @@ int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32
     if (frame_ids) {
         size_t k = 0;
         for (int w = 0; w < n_windows; w++) {
-            if (ws[w].width != c->fs_w || ws[w].height != c->fs_h)
+            if (ws[w].width != S.lay.width || ws[w].height != S.lay.height)
                 return fail(LDSO_BA_ERR_FRAME_STORE, "window size differs from the frame store's");
             for (int f = 0; f < ws[w].n_frames; f++, k++) {
-                const int s = store_find(c, frame_ids[k]);
+                const int s = S.find(frame_ids[k]);
                 if (s < 0)
                     return fail(LDSO_BA_ERR_FRAME_STORE,
                                 "frame id " + std::to_string((long long)frame_ids[k]) + " is not resident in the frame store");
@@ -5091,30 +5128,15 @@ int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32
     c->n_win = n_windows;
     c->x_stride = 0;
     c->x_prun = 0;
-    c->width = ws[0].width;
-    c->height = ws[0].height;
-    c->npix = c->width * c->height;
     c->marg = parent != nullptr;
     c->img_ext = nullptr;
     if (parent) {
-        c->img_mode = parent->img_mode;
-        c->tiles_per_row = parent->tiles_per_row;
-        c->padded_h = parent->padded_h;
-        c->frame_stride = parent->frame_stride;
-        c->img_ext = parent->d_img.p + (size_t)parent->wd[parent_win].frame_base * parent->frame_stride;
+        c->img = parent->img;
+        c->img_mode_pref = parent->img.mode;
+        c->img_ext = parent->d_img.p + (size_t)parent->wd[parent_win].frame_base * parent->img.frame_stride;
     } else {
-        // ldso_ba_load keeps the layout it had (the tuning key, or its own fallback) across loads
-        // from the store, which run in the store's layout
-        if (frame_ids) {
-            if (c->img_mode != c->fs_mode) {
-                if (c->legacy_img_mode < 0) c->legacy_img_mode = c->img_mode;
-                c->img_mode = c->fs_mode;
-            }
-        } else if (c->legacy_img_mode >= 0) {
-            c->img_mode = c->legacy_img_mode;
-            c->legacy_img_mode = -1;
-        }
-        image_geometry(c);
+        // a load from the store runs in the store's layout, ldso_ba_load in the preferred one
+        c->img = image_layout(frame_ids ? S.lay.mode : c->img_mode_pref, ws[0].width, ws[0].height);
     }
     c->wh = std::move(L.wh);
     c->wd.assign(n_windows, WinDev());
@@ -5141,7 +5163,7 @@ int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32
     const std::vector<float> neg(R, -1.0f);  // rs_energy_wo: nothing evaluated yet
     LoadList A{c};
     A.put(c->d_wins, L.wd);
-    const size_t img_n = (size_t)c->n_frames * c->frame_stride;
+    const size_t img_n = (size_t)c->n_frames * c->img.frame_stride;
     if (c->marg) {
         c->d_img.release();
         c->img_tag.clear();
@@ -5209,13 +5231,13 @@ int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32
         // store slot -> window position, device to device on the context stream, where the
         // position does not hold that slot's content already
         c->img_tag.resize((size_t)c->n_frames, 0ull);
-        const size_t bytes = (size_t)c->frame_stride * sizeof(float4);
+        const size_t bytes = c->img.slot_bytes();
         for (int p = 0; p < c->n_frames; p++) {
-            const unsigned long long seq = c->fs_seq[fslot[p]];
+            const unsigned long long seq = S.seq[fslot[p]];
             if (c->img_tag[p] == seq) continue;
             c->img_tag[p] = 0;
-            HIP_TRY(hipMemcpyAsync(c->d_img.p + (size_t)p * c->frame_stride, c->d_store.p + (size_t)fslot[p] * c->fs_stride,
-                                   bytes, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->d_img.p + (size_t)p * c->img.frame_stride, S.slot(fslot[p]), bytes,
+                                   hipMemcpyDeviceToDevice, c->stream));
             c->img_tag[p] = seq;
             c->xfer[1] += (int64_t)bytes;
         }
@@ -5223,10 +5245,10 @@ int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32
         int mismatch = 0;
         rc = stage_images(c, ws, n_windows, &mismatch);
         if (rc) return rc;
-        if (c->img_mode == 3 && mismatch) {
-            c->img_mode = 1;
-            image_geometry(c);
-            rc = c->d_img.alloc((size_t)c->n_frames * c->frame_stride);
+        if (c->img.mode == 3 && mismatch) {
+            c->img_mode_pref = 1;  // for later loads and reserves too
+            c->img = image_layout(1, c->img.width, c->img.height);
+            rc = c->d_img.alloc((size_t)c->n_frames * c->img.frame_stride);
             c->xfer[2]++;
             if (rc) return rc;
             rc = stage_images(c, ws, n_windows, &mismatch);
@@ -5244,57 +5266,36 @@ int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32
     return 0;
 }
 
-// the layout a store reserved now takes: LDSO_BA_TUNE_TILED_IMAGES (or ldso_ba_load's fallback), which
-// legacy_img_mode holds while a load from the store has img_mode
-inline int preferred_img_mode(const ldso_ba_ctx *c) { return c->legacy_img_mode >= 0 ? c->legacy_img_mode : c->img_mode; }
-
-// the slot a put of `id` writes: the id's own if it is resident, else a free one
-int store_slot_for(ldso_ba_ctx *c, int64_t id, int *slot) {
-    if (c->fs_cap == 0) return fail(LDSO_BA_ERR_FRAME_STORE, "no frame store: call ldso_ba_frames_reserve first");
-    int s = store_find(c, id);
-    for (int k = 0; s < 0 && k < c->fs_cap; k++)
-        if (!c->fs_seq[k]) s = k;
-    if (s < 0)
-        return fail(LDSO_BA_ERR_FRAME_STORE, "frame store full (" + std::to_string(c->fs_cap) +
-                                                 " slots): drop a frame before putting id " + std::to_string((long long)id));
-    *slot = s;
-    return 0;
-}
-void store_commit(ldso_ba_ctx *c, int slot, int64_t id) {
-    c->fs_id[slot] = id;
-    c->fs_seq[slot] = c->fs_next_seq++;
-    c->xfer[3]++;
-}
-
 // Device -> slot on the context stream, ordered by events and never by the host: the ingest waits for
-// what the producer's stream holds now (fs_ev_prod), and whatever that stream is given later -- the
-// producer's next overwrite of its buffers -- waits for the ingest (fs_ev_cons).  The slot itself is
+// what the producer's stream holds now (ev_prod), and whatever that stream is given later -- the
+// producer's next overwrite of its buffers -- waits for the ingest (ev_cons).  The slot itself is
 // only ever read and written on the context stream, so stream order keeps the write behind any load
 // still copying out of it.
 int store_ingest_device(ldso_ba_ctx *c, int64_t id, const float *inten, const void *texels, hipStream_t prod) {
+    FrameStore &S = c->store;
+    const ImageLayout &l = S.lay;
     int slot = -1;
-    int rc = store_slot_for(c, id, &slot);
+    int rc = S.slot_for(id, &slot);
     if (rc) return rc;
-    if (c->fs_mode == 1 && !texels)
+    if (l.mode == 1 && !texels)
         return fail(-1, "image layout 1 stores [I, dx, dy]: the device source must give the texels");
-    if (c->fs_mode == 3 && !inten)
+    if (l.mode == 3 && !inten)
         return fail(-1, "image layout 3 stores intensities: the device source must give the intensity plane");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventRecord(c->fs_ev_prod, prod));
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->fs_ev_prod, 0));
-    float4 *dst = c->d_store.p + (size_t)slot * c->fs_stride;
-    if (c->fs_mode == 3) {
-        const int wp = c->fs_tpr * 8, n = wp * (c->fs_hp / 4);
-        k_ingest_intensity<<<(n + 255) / 256, 256, 0, c->stream>>>(inten, dst, c->fs_w, c->fs_h, wp, c->fs_hp);
-    } else {
-        k_ingest_texels<<<(int)((c->fs_stride + 255) / 256), 256, 0, c->stream>>>(static_cast<const float4 *>(texels), dst,
-                                                                                 c->fs_w, c->fs_h, c->fs_tpr, c->fs_hp);
-    }
+    HIP_TRY(hipEventRecord(S.ev_prod.e, prod));
+    HIP_TRY(hipStreamWaitEvent(c->stream, S.ev_prod.e, 0));
+    const int nb = (int)((l.frame_stride + 255) / 256);  // a thread per float4 of the slot, both layouts
+    if (l.mode == 3)
+        k_ingest_intensity<<<nb, 256, 0, c->stream>>>(inten, S.slot(slot), l.width, l.height, l.tiles_per_row * 8, l.padded_h);
+    else
+        k_ingest_texels<<<nb, 256, 0, c->stream>>>(static_cast<const float4 *>(texels), S.slot(slot), l.width, l.height,
+                                                   l.tiles_per_row, l.padded_h);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->fs_ev_cons, c->stream));
-    HIP_TRY(hipStreamWaitEvent(prod, c->fs_ev_cons, 0));
-    c->xfer[1] += (int64_t)(c->fs_stride * sizeof(float4));
-    store_commit(c, slot, id);
+    HIP_TRY(hipEventRecord(S.ev_cons.e, c->stream));
+    HIP_TRY(hipStreamWaitEvent(prod, S.ev_cons.e, 0));
+    c->xfer[1] += (int64_t)l.slot_bytes();
+    S.commit(slot, id);
+    c->xfer[3]++;
     return 0;
 }
 }  // namespace
@@ -5326,70 +5327,54 @@ int ldso_ba_frames_reserve(ldso_ba_ctx *c, int32_t capacity, int32_t width, int3
     if (c->marg) return fail(-1, "a marginalisation context borrows its parent's images and has no frame store");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));  // a load may still be copying out of the old slots
-    c->fs_cap = 0;
-    c->fs_id.clear();
-    c->fs_seq.clear();
+    FrameStore &S = c->store;
+    S.cap = 0;
+    S.id.clear();
+    S.seq.clear();
     c->img_tag.clear();
-    const int mode = preferred_img_mode(c);
-    const int hp = (height + 3) / 4 * 4;
-    const int tpr = mode == 3 ? (width + 7) / 8 : (width + 1) / 2;
-    const long long stride = mode == 3 ? (long long)tpr * 8 * hp / 4 : (long long)tpr * 2 * hp;
-    int rc = c->d_store.alloc((size_t)capacity * stride);
+    S.lay = image_layout(c->img_mode_pref, width, height);
+    int rc = S.d_store.alloc((size_t)capacity * S.lay.frame_stride);
     c->xfer[2]++;
     if (rc) return rc;
-    const size_t npix = (size_t)width * height;
-    if ((rc = image_staging(c, npix))) return rc;
-    if ((rc = pin_ensure(c->pin_img, c->pin_img_n, npix * 3 * sizeof(float) + 64))) return rc;
-    if (!c->fs_ev_prod) HIP_TRY(hipEventCreateWithFlags(&c->fs_ev_prod, hipEventDisableTiming));
-    if (!c->fs_ev_cons) HIP_TRY(hipEventCreateWithFlags(&c->fs_ev_cons, hipEventDisableTiming));
-    c->fs_w = width;
-    c->fs_h = height;
-    c->fs_mode = mode;
-    c->fs_tpr = tpr;
-    c->fs_hp = hp;
-    c->fs_stride = stride;
-    c->fs_id.assign((size_t)capacity, 0);
-    c->fs_seq.assign((size_t)capacity, 0ull);
-    c->fs_cap = capacity;
+    if ((rc = image_staging(c, S.lay.npix()))) return rc;
+    if ((rc = c->pin_img.ensure(S.lay.npix() * 3 * sizeof(float) + 64))) return rc;
+    if ((rc = S.ev_prod.ensure(hipEventDisableTiming)) || (rc = S.ev_cons.ensure(hipEventDisableTiming))) return rc;
+    S.id.assign((size_t)capacity, 0);
+    S.seq.assign((size_t)capacity, 0ull);
+    S.cap = capacity;
     return 0;
 }
 
 int ldso_ba_frame_put(ldso_ba_ctx *c, int64_t frame_id, const float *dI) {
     if (!c || !dI) return fail(-1, "null argument");
+    FrameStore &S = c->store;
     int slot = -1;
-    int rc = store_slot_for(c, frame_id, &slot);
+    int rc = S.slot_for(frame_id, &slot);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t npix = (size_t)c->fs_w * c->fs_h, bytes = npix * 3 * sizeof(float);
+    const size_t npix = S.lay.npix(), bytes = npix * 3 * sizeof(float);
     if ((rc = image_staging(c, npix))) return rc;
-    if ((rc = pin_ensure(c->pin_img, c->pin_img_n, bytes + 64))) return rc;
+    if ((rc = c->pin_img.ensure(bytes + 64))) return rc;
     // every use of the pinned frame ends behind a synchronisation, so it is free here
-    std::memcpy(c->pin_img, dI, bytes);
-    int *mismatch = reinterpret_cast<int *>(c->pin_img + bytes);
+    std::memcpy(c->pin_img.p, dI, bytes);
+    int *mismatch = reinterpret_cast<int *>(c->pin_img.p + bytes);
     *mismatch = 0;
     HIP_TRY(hipMemsetAsync(c->d_img_flag.p, 0, sizeof(int), c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_img_stage.p, c->pin_img, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_img_stage.p, c->pin_img.p, bytes, hipMemcpyHostToDevice, c->stream));
     c->xfer[0] += (int64_t)bytes;
-    float4 *dst = c->d_store.p + (size_t)slot * c->fs_stride;
-    if (c->fs_mode == 3) {
-        const long long n = (long long)c->fs_tpr * 8 * c->fs_hp;
-        k_intensity_image<<<(int)((n + 255) / 256), 256, 0, c->stream>>>(c->d_img_stage.p, reinterpret_cast<float *>(dst),
-                                                                         c->fs_w, c->fs_h, c->fs_tpr, c->fs_hp, c->d_img_flag.p);
-    } else {
-        k_tile_image<<<(int)((c->fs_stride + 255) / 256), 256, 0, c->stream>>>(c->d_img_stage.p, dst, c->fs_w, c->fs_h,
-                                                                              c->fs_tpr, c->fs_hp);
-    }
+    launch_repack(S.lay, c->d_img_stage.p, S.slot(slot), c->d_img_flag.p, c->stream);
     HIP_TRY(hipGetLastError());
-    if (c->fs_mode == 3) HIP_TRY(hipMemcpyAsync(mismatch, c->d_img_flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (S.lay.mode == 3) HIP_TRY(hipMemcpyAsync(mismatch, c->d_img_flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->fs_mode == 3 && *mismatch) {
-        c->fs_seq[slot] = 0;  // the slot holds intensities whose recomputed gradients are not the caller's
+    if (S.lay.mode == 3 && *mismatch) {
+        S.seq[slot] = 0;  // the slot holds intensities whose recomputed gradients are not the caller's
         return fail(LDSO_BA_ERR_GRADIENT_MISMATCH,
                     "frame id " + std::to_string((long long)frame_id) +
                         ": dI's gradients are not makeImages' (FrameHessian.cc:96-101), which image layout 3 recomputes; "
                         "reserve the frame store in layout 1 (LDSO_BA_TUNE_TILED_IMAGES = 1 before ldso_ba_frames_reserve)");
     }
-    store_commit(c, slot, frame_id);
+    S.commit(slot, frame_id);
+    c->xfer[3]++;
     return 0;
 }
 
@@ -5402,48 +5387,51 @@ int ldso_ba_frame_put_device(ldso_ba_ctx *c, int64_t frame_id, const float *dev_
 
 int ldso_ba_frame_put_tracker(ldso_ba_ctx *c, int64_t frame_id, const ldso_ct_ctx *tracker) {
     if (!c || !tracker) return fail(-1, "null argument");
-    if (c->fs_cap == 0) return fail(LDSO_BA_ERR_FRAME_STORE, "no frame store: call ldso_ba_frames_reserve first");
+    const ImageLayout &l = c->store.lay;
+    if (c->store.cap == 0) return fail(LDSO_BA_ERR_FRAME_STORE, "no frame store: call ldso_ba_frames_reserve first");
     ldso_ba::CtFrameView v{};
     int rc = ldso_ba::ct_frame_view(tracker, &v);
     if (rc) return rc;
     if (v.device != c->device) return fail(-1, "tracker and context are on different devices");
-    if (v.width != c->fs_w || v.height != c->fs_h)
+    if (v.width != l.width || v.height != l.height)
         return fail(LDSO_BA_ERR_FRAME_STORE, "tracker frame is " + std::to_string(v.width) + "x" + std::to_string(v.height) +
-                                                 ", the frame store holds " + std::to_string(c->fs_w) + "x" +
-                                                 std::to_string(c->fs_h));
+                                                 ", the frame store holds " + std::to_string(l.width) + "x" +
+                                                 std::to_string(l.height));
     if (!v.have_frame) return fail(-1, "the tracker has no new frame: ldso_ct_set_new_frame not called");
     return store_ingest_device(c, frame_id, v.intensity, v.texels, static_cast<hipStream_t>(v.stream));
 }
 
 int ldso_ba_frame_drop(ldso_ba_ctx *c, int64_t frame_id) {
     if (!c) return fail(-1, "null ctx");
-    const int s = store_find(c, frame_id);
+    const int s = c->store.find(frame_id);
     if (s < 0)
         return fail(LDSO_BA_ERR_FRAME_STORE, "frame id " + std::to_string((long long)frame_id) + " is not resident in the frame store");
-    c->fs_seq[s] = 0;  // the next put into the slot is ordered behind its readers on the context stream
+    c->store.seq[s] = 0;  // the next put into the slot is ordered behind its readers on the context stream
     return 0;
 }
 
 int ldso_ba_frame_get(ldso_ba_ctx *c, int64_t frame_id, float *intensity, float *grad) {
     if (!c || !intensity) return fail(-1, "null argument");
-    const int s = store_find(c, frame_id);
+    const FrameStore &S = c->store;
+    const ImageLayout &l = S.lay;
+    const int s = S.find(frame_id);
     if (s < 0)
         return fail(LDSO_BA_ERR_FRAME_STORE, "frame id " + std::to_string((long long)frame_id) + " is not resident in the frame store");
-    if (grad && c->fs_mode != 1) return fail(-1, "image layout 3 stores no gradients: grad must be NULL");
+    if (grad && l.mode != 1) return fail(-1, "image layout 3 stores no gradients: grad must be NULL");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t npix = (size_t)c->fs_w * c->fs_h;
+    const size_t npix = l.npix();
     int rc = image_staging(c, npix);
     if (rc) return rc;
-    if ((rc = pin_ensure(c->pin_img, c->pin_img_n, npix * 3 * sizeof(float) + 64))) return rc;
+    if ((rc = c->pin_img.ensure(npix * 3 * sizeof(float) + 64))) return rc;
     float *d_i = c->d_img_stage.p, *d_g = c->d_img_stage.p + npix;
-    k_slot_unpack<<<(int)((npix + 255) / 256), 256, 0, c->stream>>>(c->d_store.p + (size_t)s * c->fs_stride, c->fs_mode, d_i,
-                                                                    d_g, c->fs_w, c->fs_h, c->fs_tpr);
+    k_slot_unpack<<<(int)((npix + 255) / 256), 256, 0, c->stream>>>(S.slot(s), l.mode, d_i, d_g, l.width, l.height,
+                                                                    l.tiles_per_row);
     HIP_TRY(hipGetLastError());
     const size_t n = npix * (grad ? 3 : 1);
-    HIP_TRY(hipMemcpyAsync(c->pin_img, d_i, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->pin_img.p, d_i, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    std::memcpy(intensity, c->pin_img, npix * sizeof(float));
-    if (grad) std::memcpy(grad, c->pin_img + npix * sizeof(float), 2 * npix * sizeof(float));
+    std::memcpy(intensity, c->pin_img.p, npix * sizeof(float));
+    if (grad) std::memcpy(grad, c->pin_img.p + npix * sizeof(float), 2 * npix * sizeof(float));
     return 0;
 }
 
@@ -5508,9 +5496,9 @@ int ldso_ba_update_points(ldso_ba_ctx *c, int32_t win, const float *vals) {
     HIP_TRY(hipSetDevice(c->device));
     int rc = c->d_pt_vals.ensure((size_t)c->P_tot);
     if (rc) return rc;
-    if ((rc = pin_ensure(c->pin_out, c->pin_out_n, (size_t)H.P * sizeof(float4)))) return rc;
+    if ((rc = c->pin_out.ensure((size_t)H.P * sizeof(float4)))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));  // pin_out may feed an earlier copy
-    float4 *st = reinterpret_cast<float4 *>(c->pin_out);
+    float4 *st = reinterpret_cast<float4 *>(c->pin_out.p);
     for (int q = 0; q < H.P; q++) {
         const float *v = vals + 4 * (size_t)H.pt_orig[q];
         st[q] = make_float4(v[0], v[1], v[2], v[3]);
@@ -5533,10 +5521,10 @@ int ldso_ba_update_residuals(ldso_ba_ctx *c, int32_t win, const int8_t *state, c
     if (!state || !state_energy || !new_energy || !flags) return fail(-1, "bad arguments");
     HIP_TRY(hipSetDevice(c->device));
     const size_t R = (size_t)D.R;
-    int rc = pin_ensure(c->pin_out, c->pin_out_n, R * (2 * sizeof(float) + 2));
+    int rc = c->pin_out.ensure(R * (2 * sizeof(float) + 2));
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    float *se = reinterpret_cast<float *>(c->pin_out), *ne = se + R;
+    float *se = reinterpret_cast<float *>(c->pin_out.p), *ne = se + R;
     int8_t *st = reinterpret_cast<int8_t *>(ne + R);
     uint8_t *fl = reinterpret_cast<uint8_t *>(st + R);
     for (size_t pos = 0; pos < R; pos++) {
@@ -5695,8 +5683,8 @@ static int linearize_pass(ldso_ba_ctx *c, int fix, int accumulate, const Switche
     hipStream_t st = c->stream;
     if (L.n_items > 0) {
         rc = timed_launch_ext(c, 0, [&](hipEvent_t a, hipEvent_t b) {
-            if (c->marg) launch_linearize<true>(c->img_mode, L.n_blocks, st, L, a, b);
-            else launch_linearize<false>(c->img_mode, L.n_blocks, st, L, a, b);
+            if (c->marg) launch_linearize<true>(c->img.mode, L.n_blocks, st, L, a, b);
+            else launch_linearize<false>(c->img.mode, L.n_blocks, st, L, a, b);
         });
         if (rc) return rc;
     }
@@ -5797,8 +5785,8 @@ int ldso_ba_linearize_residuals(ldso_ba_ctx *c, int32_t win, int8_t *new_state, 
     L.n_items = D.n_top_items;
     L.n_blocks = (L.n_items + 3) / 4;
     rc = timed_launch(c, 0, st, [&] {
-        if (c->marg) launch_linearize<true>(c->img_mode, L.n_blocks, st, L);
-        else launch_linearize<false>(c->img_mode, L.n_blocks, st, L);
+        if (c->marg) launch_linearize<true>(c->img.mode, L.n_blocks, st, L);
+        else launch_linearize<false>(c->img.mode, L.n_blocks, st, L);
     });
     if (rc) return rc;
     std::vector<int8_t> ns(R);
@@ -5855,9 +5843,9 @@ int ldso_ba_activate_points(ldso_ba_ctx *c, int32_t win, int32_t n, const ldso_c
     A.precalc = c->d_precalc.p;
     A.pts = c->d_act_in.p;
     A.out = c->d_act_out.p;
-    A.frame_stride = c->frame_stride;
-    A.tpr = c->tiles_per_row;
-    A.img_mode = c->img_mode;
+    A.frame_stride = c->img.frame_stride;
+    A.tpr = c->img.tiles_per_row;
+    A.img_mode = c->img.mode;
     A.win = win;
     A.n = n;
     A.min_obs = min_obs;
@@ -5911,13 +5899,9 @@ int ldso_ba_get_energy(ldso_ba_ctx *c, int32_t win, double *out) {
 
 // n point steps from point `base` on into pin_step (grown as needed), synchronised
 static int fetch_point_steps(ldso_ba_ctx *c, int base, int n) {
-    if (c->pin_step_n < (size_t)n) {
-        if (c->pin_step) (void)hipHostFree(c->pin_step);
-        c->pin_step = nullptr;
-        HIP_TRY(hipHostMalloc(&c->pin_step, std::max<size_t>(1, n) * sizeof(float), hipHostMallocDefault));
-        c->pin_step_n = n;
-    }
-    if (n) HIP_TRY(hipMemcpyAsync(c->pin_step, c->d_pt_step.p + base, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    int rc = c->pin_step.ensure((size_t)n);
+    if (rc) return rc;
+    if (n) HIP_TRY(hipMemcpyAsync(c->pin_step.p, c->d_pt_step.p + base, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     return ldso_ba_sync(c);
 }
 
@@ -5931,17 +5915,12 @@ static int fetch_sys(ldso_ba_ctx *c, int win) {
     if (c->sys_valid[win]) return 0;
     const WinDev &D = c->wd[win];
     const size_t n = (size_t)sys_len(D.D);
-    if (c->pin_sys_n < n) {
-        if (c->pin_sys) (void)hipHostFree(c->pin_sys);
-        c->pin_sys = nullptr;
-        HIP_TRY(hipHostMalloc(&c->pin_sys, n * sizeof(double), hipHostMallocDefault));
-        c->pin_sys_n = n;
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(c->pin_sys, c->d_sys.p + D.sys_base, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    int rc = ldso_ba_sync(c);
+    int rc = c->pin_sys.ensure(n);
     if (rc) return rc;
-    std::memcpy(c->sys_host.data() + D.sys_base, c->pin_sys, n * sizeof(double));
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(c->pin_sys.p, c->d_sys.p + D.sys_base, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = ldso_ba_sync(c))) return rc;
+    std::memcpy(c->sys_host.data() + D.sys_base, c->pin_sys.p, n * sizeof(double));
     c->sys_valid[win] = 1;
     return 0;
 }
@@ -6083,12 +6062,12 @@ int ldso_ba_resubstitute(ldso_ba_ctx *c, int32_t win, const double *x, double la
     const int N = H.N;
     // xAd[N*h + t] = x_h^T adHostF[h + N t] + x_t^T adTargetF[h + N t] (EnergyFunctional.cc:624-632)
     const size_t nx = (size_t)N * N * 8 + 4;
-    if (!c->pin_xad)
-        HIP_TRY(hipHostMalloc(&c->pin_xad, ((size_t)LDSO_BA_MAX_FRAMES * LDSO_BA_MAX_FRAMES * 8 + 4) * sizeof(float),
-                              hipHostMallocDefault));
+    // the largest window's size, once
+    int rc = c->pin_xad.ensure((size_t)LDSO_BA_MAX_FRAMES * LDSO_BA_MAX_FRAMES * 8 + 4);
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));  // a previous upload from pin_xad has completed
     std::vector<float> xF(D.D);
-    float *host = c->pin_xad;
+    float *host = c->pin_xad.p;
     for (int i = 0; i < D.D; i++) xF[i] = (float)x[i];
     for (int h = 0; h < N; h++)
         for (int t = 0; t < N; t++) {
@@ -6110,7 +6089,7 @@ int ldso_ba_resubstitute(ldso_ba_ctx *c, int32_t win, const double *x, double la
     if (point_step_out) {
         int rc = fetch_point_steps(c, D.point_base, D.P);
         if (rc) return rc;
-        for (int q = 0; q < D.P; q++) point_step_out[H.pt_orig[q]] = c->pin_step[q];
+        for (int q = 0; q < D.P; q++) point_step_out[H.pt_orig[q]] = c->pin_step.p[q];
     }
     return 0;
 }
@@ -6249,7 +6228,7 @@ int ldso_ba_resubstitute_device(ldso_ba_ctx *c, double lambda, float *point_step
     if (point_step_out) {
         int rc = fetch_point_steps(c, 0, c->P_tot);
         if (rc) return rc;
-        scatter_points(c, c->pin_step, point_step_out);
+        scatter_points(c, c->pin_step.p, point_step_out);
     }
     return 0;
 }
@@ -6272,10 +6251,7 @@ std::vector<unsigned long long> capture_key(const ldso_ba_ctx *c, const Switches
 template <typename F>
 int launch_cached_graph(ldso_ba_ctx *c, ldso_ba_ctx::Graph &g, const std::vector<unsigned long long> &key, F &&body) {
     const unsigned long long gen = g_alloc_gen.load();
-    if (g.exec && (g.gen != gen || g.key != key)) {
-        (void)hipGraphExecDestroy(g.exec);
-        g.exec = nullptr;
-    }
+    if (g.exec && (g.gen != gen || g.key != key)) g.reset();
     if (!g.exec) {
         hipGraph_t gr = nullptr;
         HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
@@ -6345,18 +6321,14 @@ int ldso_ba_iterate(ldso_ba_ctx *c, int32_t iteration, double lambda, const doub
     const size_t xb = (size_t)c->vec_total * sizeof(double), eb = (size_t)2 * c->n_win * sizeof(double),
                  sb = (size_t)c->P_tot * sizeof(float);
     if ((rc = pin_map_ensure(c, xb + eb + sb))) return rc;
-    const double *px = reinterpret_cast<const double *>(c->pin_map), *pe = px + c->vec_total;
+    const double *px = reinterpret_cast<const double *>(c->pin_map.p), *pe = px + c->vec_total;
     const float *ps = reinterpret_cast<const float *>(pe + 2 * c->n_win);
     {
         PackOut K{};
-        auto seg = [&](const void *src, size_t off, size_t bytes) {
-            K.src[K.n_seg] = static_cast<const unsigned *>(src);
-            K.dst[K.n_seg] = reinterpret_cast<unsigned *>(c->pin_map_dev + off);
-            K.words[K.n_seg++] = (int)(bytes / 4);
-        };
-        if (x_out) seg(c->d_x.p, 0, xb);
-        if (energy_out) seg(c->win_energy(), xb, eb);
-        if (point_step_out && sb) seg(c->d_pt_step.p, xb + eb, sb);
+        char *pd = c->pin_map.dev;
+        if (x_out) pack_seg(K, c->d_x.p, pd, xb);
+        if (energy_out) pack_seg(K, c->win_energy(), pd + xb, eb);
+        if (point_step_out && sb) pack_seg(K, c->d_pt_step.p, pd + xb + eb, sb);
         if (K.n_seg) {
             k_pack_out<<<std::min(64, (int)((xb + eb + sb) / 1024) + 1), 256, 0, c->stream>>>(K);
             HIP_TRY(hipGetLastError());
@@ -6570,21 +6542,16 @@ int ldso_ba_optimize(ldso_ba_ctx *c, int32_t n_its, const ldso_ba_opt_settings *
     const size_t o_f = up16(hb), o_c = o_f + up16(fb), o_w = o_c + up16(cb), o_t = o_w + up16(wb), o_s = o_t + up16(tb),
                  o_u = o_s + up16(sb), o_i = o_u + up16(sb);
     if ((rc = pin_map_ensure(c, o_i + ib))) return rc;
-    char *po = c->pin_map, *pd = c->pin_map_dev;
+    char *po = c->pin_map.p, *pd = c->pin_map.dev;
     {  // one launch writes every result into the mapped buffer (the idepth column only)
         PackOut K{};
-        auto seg = [&](const void *src, size_t off, size_t bytes) {
-            K.src[K.n_seg] = static_cast<const unsigned *>(src);
-            K.dst[K.n_seg] = reinterpret_cast<unsigned *>(pd + off);
-            K.words[K.n_seg++] = (int)(bytes / 4);
-        };
-        if (energy_out) seg(c->d_ehist.p, 0, hb);
-        if (frames_out) seg(c->d_fstate.p, o_f, fb);
-        if (calib_out) seg(c->d_calib_val.p, o_c, cb);
-        seg(c->d_wins.p, o_w, wb);  // the host mirror of WinDev (calibration, cDeltaF) follows the device
-        seg(c->d_frame_th.p, o_t, tb);  // setNewFrameEnergyTH of the last pass (ldso_ba_get_frame_energy_th)
-        seg(c->d_stop.p, o_s, sb);      // the loop exits
-        seg(c->d_status.p, o_u, sb);
+        if (energy_out) pack_seg(K, c->d_ehist.p, pd, hb);
+        if (frames_out) pack_seg(K, c->d_fstate.p, pd + o_f, fb);
+        if (calib_out) pack_seg(K, c->d_calib_val.p, pd + o_c, cb);
+        pack_seg(K, c->d_wins.p, pd + o_w, wb);  // the host mirror of WinDev (calibration, cDeltaF) follows the device
+        pack_seg(K, c->d_frame_th.p, pd + o_t, tb);  // setNewFrameEnergyTH of the last pass (ldso_ba_get_frame_energy_th)
+        pack_seg(K, c->d_stop.p, pd + o_s, sb);      // the loop exits
+        pack_seg(K, c->d_status.p, pd + o_u, sb);
         if (idepth_out && c->P_tot) {
             K.pt_data = c->d_pt_data.p;
             K.idepth_dst = reinterpret_cast<float *>(pd + o_i);
@@ -6732,7 +6699,7 @@ int ldso_ba_set_tuning(ldso_ba_ctx *c, int32_t key, int32_t value) {
     if (key == LDSO_BA_TUNE_TILED_IMAGES) {
         if (c->n_win) return fail(-1, "image layout must be chosen before ldso_ba_load");
         if (value != 1 && value != 3) return fail(-1, "image layout must be 1 or 3");
-        c->img_mode = value;
+        c->img_mode_pref = value;
         return 0;
     }
     if (key == LDSO_BA_TUNE_ITEM_ORDER) {
@@ -6770,10 +6737,10 @@ int ldso_ba_set_kernel_timing(ldso_ba_ctx *c, int32_t enable) {
     }
     // the events the timed launches will take, created now: hipEventCreate is a host call of tens of
     // us, which inside a timed loop would stall the launches (kept in the pool across calls)
-    while (c->timing && c->ev_pool.size() < 256) {
+    while (c->timing && c->ev_pool.free.size() < 256) {
         hipEvent_t e;
         if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) break;
-        c->ev_pool.push_back(e);
+        c->ev_pool.free.push_back(e);
     }
     return 0;
 }
@@ -6795,7 +6762,7 @@ int32_t ldso_ba_num_kernels(void) { return kNumKernels; }
 int ldso_ba_stats(ldso_ba_ctx *c, int64_t *device_bytes, int64_t *n_points, int64_t *n_residuals) {
     if (!c) return fail(-1, "null ctx");
     if (device_bytes)
-        *device_bytes = (int64_t)(c->d_img.bytes() + c->d_store.bytes() + c->d_precalc.bytes() + c->d_pt_data.bytes() + c->d_rec_a.bytes() + c->d_rec_b.bytes() +
+        *device_bytes = (int64_t)(c->d_img.bytes() + c->store.d_store.bytes() + c->d_precalc.bytes() + c->d_pt_data.bytes() + c->d_rec_a.bytes() + c->d_rec_b.bytes() +
                                   c->d_top_slab.bytes() + c->d_sc_slab.bytes() + c->d_sys.bytes());
     if (n_points) *n_points = c->P_tot;
     if (n_residuals) *n_residuals = c->R_tot;

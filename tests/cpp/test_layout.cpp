@@ -475,6 +475,33 @@ void check_rejections() {
     }
 }
 
+// image_layout against values worked out by hand from its rules: padded_h = (h+3)/4*4; mode 3:
+// tpr = (w+7)/8, stride = tpr*8*padded_h/4; mode 1: tpr = (w+1)/2, stride = tpr*2*padded_h
+void check_image_layout() {
+    g_case = "image_layout";
+    static const struct {
+        int w, h, mode, tpr, hp;
+        long long stride, repack;
+    } kCases[] = {
+        {13, 7, 3, 2, 8, 32, 128},
+        {13, 7, 1, 7, 8, 112, 112},
+        {162, 118, 3, 21, 120, 5040, 20160},
+        {162, 118, 1, 81, 120, 19440, 19440},
+        {640, 480, 3, 80, 480, 76800, 307200},
+        {640, 480, 1, 320, 480, 307200, 307200},
+    };
+    for (const auto &k : kCases) {
+        const ImageLayout l = image_layout(k.mode, k.w, k.h);
+        CHECK(l.mode == k.mode && l.width == k.w && l.height == k.h);
+        CHECK(l.tiles_per_row == k.tpr);
+        CHECK(l.padded_h == k.hp);
+        CHECK(l.frame_stride == k.stride);
+        CHECK(l.npix() == (size_t)k.w * k.h);
+        CHECK(l.slot_bytes() == (size_t)k.stride * 16);
+        CHECK(l.repack_elems() == k.repack);  // mode 3: one per padded intensity, 4 to a float4
+    }
+}
+
 }  // namespace
 
 int main() {
@@ -507,6 +534,7 @@ int main() {
     check_case("three windows", {make_win(7, 120, 31, 3), make_win(3, 50, 32, 0), make_win(13, 45, 33, 6)});
     check_marg_and_auto_chunk();
     check_rejections();
+    check_image_layout();
     std::printf("%lld checks, %d failure(s)\n", g_checks, g_fail);
     return g_fail ? 1 : 0;
 }

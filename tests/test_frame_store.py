@@ -348,6 +348,54 @@ def test_errors_are_codes_and_messages(built):
     c1.close()
 
 
+# ---- 6b. a store whose layout differs from the loads' -------------------------------------------
+def test_store_layout_differs_from_load_layout(built):
+    """The store keeps the layout it was reserved in (1), ldso_ba_load the preferred one (3): loads
+    by id run in the store's layout without changing the preference, a plain load returns to it, a
+    new store takes it, and ldso_ba_load's gradient fallback becomes it."""
+    name = "N3P64_160x120"
+    w = window(name)
+    ids = [40 + f for f in range(w.n_frames)]
+    c = make_ctx(1, w.n_frames, w)
+    c.set_tuning(TILED_IMAGES, 3)  # nothing is loaded yet
+    # (a) a plain load, in layout 3
+    c.load([w])
+    check_pass(c, name)
+    bytes_a = c.stats()["device_bytes"]
+    # (b) by id, in the store's layout 1: the window's image array is four times layout 3's
+    for f, i in enumerate(ids):
+        c.frame_put(i, w.dI[f])
+    c.load([without_images(window(name))], frame_ids=ids)
+    check_pass(c, name)
+    assert c.stats()["device_bytes"] == bytes_a + w.n_frames * (slot_bytes(w, 1) - slot_bytes(w, 3))
+    # (c) a plain load again: one image allocation (no fallback's second), back in layout 3
+    s0 = c.transfer_stats()
+    c.load([window(name)])
+    check_pass(c, name)
+    assert delta(s0, c.transfer_stats())["allocs"] == 1
+    assert c.stats()["device_bytes"] == bytes_a
+    # (d) a store reserved while a load by id is active takes the preference, 3
+    c.load([without_images(window(name))], frame_ids=ids)
+    c.frames_reserve(w.n_frames, w.width, w.height)
+    c.frame_put(ids[0], w.dI[0])
+    with raises(-1, "layout 3"):
+        c.frame_get(ids[0], with_grad=True)
+    c.close()
+
+    # (e) ldso_ba_load's fallback to layout 1 is the preference of a store reserved afterwards
+    bad = window(name)
+    bad.dI = bad.dI.copy()
+    bad.dI[:, :, 1] += np.float32(0.125)
+    c = BAContext(0)
+    c.set_tuning(TILED_IMAGES, 3)
+    c.load([bad])
+    c.frames_reserve(1, w.width, w.height)
+    c.frame_put(7, bad.dI[0])
+    _, g = c.frame_get(7, with_grad=True)
+    np.testing.assert_array_equal(g, bad.dI[0][:, 1:3])
+    c.close()
+
+
 # ---- 7. marginalisation context over a parent loaded by id ------------------------------------
 def test_marginalization_context_borrows_images_loaded_by_id(built):
     name = "N5P400_162x118"

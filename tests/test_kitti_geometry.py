@@ -9,7 +9,7 @@ The KITTI sequences themselves are not here, so the windows are synthetic (ldso_
     k_linearize's pipelined loop) and many pattern pixels leaving the image (OOB);
   * KITTI03_RAW: examples/Kitti/Kitti03.txt's raw 1242 x 375 frame, a width that is not a multiple
     of the 8-pixel image tiles and a height that is not a multiple of the 4-row tiles (the padded
-    tiles of image_geometry), with points in the border band;
+    tiles of image_layout), with points in the border band;
   * the same 1242 x 375 frame with sideways travel, whose border points stay near the border in
     every target (residuals whose taps reach the last columns / rows).
 The KITTI driver fixes both affine modes to 0 (run_dso_kitti.cc:299-300): every GPU test here runs
