@@ -108,8 +108,9 @@ class LdsoBaWindow(C.Structure):
 
 
 def source_sha256() -> str | None:
-    """sha256 over the sources libldso_ba.so is built from (ldso_amd/csrc, include/ldso_ba.h): the
-    identity of a build that survives a rebuild on another machine (the .so bytes do not)."""
+    """sha256 over the sources libldso_ba.so is built from (ldso_amd/csrc, include/ldso_ba.h,
+    include/ldso_ct.h): the identity of a build that survives a rebuild on another machine (the .so
+    bytes do not)."""
     import glob
     import hashlib
 
@@ -117,7 +118,8 @@ def source_sha256() -> str | None:
     files = sorted(glob.glob(os.path.join(root, "ldso_amd", "csrc", "*.hip")) +
                    glob.glob(os.path.join(root, "ldso_amd", "csrc", "*.h")) +
                    glob.glob(os.path.join(root, "ldso_amd", "csrc", "*.cpp")) +
-                   [os.path.join(root, "ldso_amd", "csrc", "Makefile"), os.path.join(root, "include", "ldso_ba.h")])
+                   [os.path.join(root, "ldso_amd", "csrc", "Makefile"), os.path.join(root, "include", "ldso_ba.h"),
+                    os.path.join(root, "include", "ldso_ct.h")])
     h = hashlib.sha256()
     try:
         for f in files:
