@@ -324,6 +324,21 @@ public:
     // pass on first use
     ResState residualState(int mirrorIdx);
     const float *residualCenter(int mirrorIdx);
+    // CoarseTracker::setCoarseTrackingRef -> makeCoarseDepthL0 (CoarseTracker.cc:347-538) of
+    // `tracker` from this window's last device pass, device to device
+    // (ldso_ct_make_reference_ba): the cloud of every level from the centerProjectedTo and HdiF of
+    // the points whose residual to the newest keyframe is IN; no centre, state or cloud crosses to
+    // the host.  frame_src: the tracker context whose current new frame is that keyframe (NULL:
+    // `tracker` itself); ab_exposure, a, b: the keyframe's ab_exposure and aff_g2l().  The call
+    // belongs where FullSystem::makeKeyFrame has it (FullSystem.cc:613-621): after optimize and
+    // removeOutliers, before flagPointsForRemoval.  The points removeOutliers drops have no
+    // residual left and contribute nothing, and a residual linearizeAll(true) found inactive is
+    // not IN, so calling it before the face applies that structural change to the device gives
+    // the reference's cloud.  Once the mirror has been rebuilt (any pass, solve or residual method
+    // after a structural change reloads the window) the pass is gone: the call then fails, with
+    // ok() false and lastError() set, until the next linearizeAll / optimize.  Returns ok().
+    bool setCoarseTrackingRef(ldso_ct_ctx *tracker, const ldso_ct_ctx *frame_src, double ab_exposure, double a,
+                              double b);
     // device linearisation passes run so far (linearizeAll, the per-residual relinearisation,
     // every pass of optimize): one per call site
     long devicePasses() const { return passes_; }

@@ -11,8 +11,11 @@
  *   CoarseTracker::calcGSSSE            src/frontend/CoarseTracker.cc:675-741 -> ldso_ct_calc_gs
  *     with Accumulator9                 include/internal/OptimizationBackend/MatrixAccumulators.h:1104-1643
  *
- * The reference frame's point cloud (pc_u/pc_v/pc_idepth/pc_color per pyramid level, the output
- * of CoarseTracker::makeCoarseDepthL0, CoarseTracker.cc:357-538) is handed over by
+ *   CoarseTracker::makeCoarseDepthL0    src/frontend/CoarseTracker.cc:357-538 -> ldso_ct_make_reference
+ *                                                                              (+ _ba: from a BA pass)
+ *
+ * The reference frame's point cloud (pc_u/pc_v/pc_idepth/pc_color per pyramid level) is built on
+ * the device by ldso_ct_make_reference / ldso_ct_make_reference_ba, or handed over ready-made by
  * ldso_ct_set_reference; trackNewestCoarse's LM loop (CoarseTracker.cc:61-310) stays with the
  * caller and calls these entry points exactly where it calls calcRes / calcGSSSE.
  *
@@ -64,6 +67,41 @@ int ldso_ct_set_reference(ldso_ct_ctx *ctx, const int32_t *pc_n, const float *co
                           const float *const *pc_v, const float *const *pc_idepth,
                           const float *const *pc_color, double ref_ab_exposure, double ref_aff_a,
                           double ref_aff_b);
+
+/* CoarseTracker::makeCoarseDepthL0 (CoarseTracker.cc:357-538) on the device: the cloud of every
+ * level from n contributions, one per active point whose lastResiduals[0] targets the reference
+ * frame with state IN, already filtered and in the reference's traversal order (frames in window
+ * order, each frame's features in order): center [n][3] = r->centerProjectedTo, hdi [n] =
+ * ph->HdiF.  The per-pixel sums of the scatter run in that order, so the cloud is the reference's
+ * bit for bit.  A centre whose pixel (int(c[0] + 0.5f), int(c[1] + 0.5f)) falls outside
+ * [0, w) x [0, h) -- the reference would write outside its arrays there, undefined behaviour --
+ * contributes nothing, and nothing is ever read outside the maps.
+ * frame_src: the tracker context whose current new frame (ldso_ct_set_new_frame) is the reference
+ * keyframe, the source of pc_color = dIp[lvl][i][0]; NULL = ctx itself; another context (the
+ * reference's coarseTracker_forNewKF / coarseTracker pair) must be on the same device and of the
+ * same size, and is read on the device, ordered by events.
+ * Leaves ctx as ldso_ct_set_reference does (the cloud, the exposure and affine pair, the warped
+ * buffers invalidated).  pc_n_out (may be NULL): [levels] points per level.  The cloud and the
+ * maps never leave the device: only the counts come back, behind one synchronisation. */
+int ldso_ct_make_reference(ldso_ct_ctx *ctx, const ldso_ct_ctx *frame_src, int32_t n, const float *center,
+                           const float *hdi, double ref_ab_exposure, double ref_aff_a, double ref_aff_b,
+                           int32_t *pc_n_out);
+/* The same from the last pass of a bundle-adjustment context, device to device (what
+ * FullSystem::makeKeyFrame does after optimize, FullSystem.cc:613-621): the contributions are, for
+ * the points of window `win` in the context's device point order (host frame, then point_rank),
+ * each point's residual whose target is ref_frame (-1 = the window's last frame), if it exists and
+ * its state is IN: its centre and the point's HdiF (the values ldso_ba_get_residuals /
+ * ldso_ba_get_points return).  Refused (< 0): null arguments, another device, win or ref_frame out
+ * of range, a marginalisation context, a context holding a shard of its points (a communicator of
+ * more than one rank, or loaded with shard_count > 1), no pass since the context's last load, a
+ * tracker frame size that differs from the window's images. */
+struct ldso_ba_ctx;
+int ldso_ct_make_reference_ba(ldso_ct_ctx *ctx, const ldso_ct_ctx *frame_src, const struct ldso_ba_ctx *ba,
+                              int32_t win, int32_t ref_frame, double ref_ab_exposure, double ref_aff_a,
+                              double ref_aff_b, int32_t *pc_n_out);
+/* read back level lvl of the resident cloud, whichever call made it: out [n][4] = {u, v, idepth,
+ * color}; *n_out = pc_n[lvl]; out may be NULL to query n. */
+int ldso_ct_get_reference(ldso_ct_ctx *ctx, int32_t lvl, int32_t *n_out, float *out, int32_t capacity);
 
 /* CoarseTracker::calcRes(lvl, refToNew, aff_g2l, cutoffTH) -> rs_out[6]; also keeps the warped
  * buffers on the device for the next ldso_ct_calc_gs (as the reference keeps buf_warped_*). */

@@ -240,6 +240,11 @@ CT_ABI = [
     ("ldso_ct_get_frame_level", C.c_int, [C.c_void_p, C.c_int32, f32p, f32p]),
     ("ldso_ct_set_reference", C.c_int,
      [C.c_void_p, i32p, f32pp, f32pp, f32pp, f32pp, C.c_double, C.c_double, C.c_double]),
+    ("ldso_ct_make_reference", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_int32, f32p, f32p, C.c_double, C.c_double, C.c_double, i32p]),
+    ("ldso_ct_make_reference_ba", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, i32p]),
+    ("ldso_ct_get_reference", C.c_int, [C.c_void_p, C.c_int32, i32p, f32p, C.c_int32]),
     ("ldso_ct_calc_res", C.c_int, [C.c_void_p, C.c_int32, f64p, C.c_double, C.c_double, C.c_float, f64p]),
     ("ldso_ct_calc_res_batch", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, f64p, f64p, C.c_float, f64p]),
     ("ldso_ct_calc_gs", C.c_int, [C.c_void_p, C.c_int32, f64p, C.c_double, C.c_double, f64p, f64p]),

@@ -3,6 +3,7 @@
 // or by the library's host helpers (precalc, adjoints, priors, deltas, energies, nullspaces,
 // solve, frame marginalisation).
 #include "../../include/ldso_amd/energy_functional.h"
+#include "../../include/ldso_ct.h"
 
 #include <algorithm>
 #include <cstring>
@@ -893,6 +894,24 @@ const float *EnergyFunctional::residualCenter(int k) {
         outCenterPass_ = passes_;
     }
     return &outCenter_[3 * (size_t)k];
+}
+
+bool EnergyFunctional::setCoarseTrackingRef(ldso_ct_ctx *tracker, const ldso_ct_ctx *frame_src, double ab_exposure,
+                                            double a, double b) {
+    if (!tracker) {
+        err_ = "setCoarseTrackingRef: null tracker";
+        return false;
+    }
+    if (!ctx_) {
+        if (err_.empty()) err_ = "setCoarseTrackingRef: no device context";
+        return false;
+    }
+    // the library refuses a context that was loaded after its last pass (a rebuilt mirror)
+    if (ldso_ct_make_reference_ba(tracker, frame_src, ctx_, 0, -1, ab_exposure, a, b, nullptr)) {
+        fail("ldso_ct_make_reference_ba");
+        return false;
+    }
+    return ok();
 }
 
 void EnergyFunctional::syncResiduals() {

@@ -3285,6 +3285,10 @@ struct ldso_ba_ctx {
     // after a load) and its staging buffers
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 1;
+    // the shard count of the last load, and whether a linearisation pass has run since it
+    // (ldso_ct_make_reference_ba reads the pass's centres and HdiF of whole windows only)
+    int shard_count = 1;
+    bool pass_since_load = false;
     int64_t x_stride = 0;
     int64_t x_prun = 0;  // |idepth| run length per window slot (max local points over windows and ranks)
     DevBuf<float> d_x_local, d_x_gathered;
@@ -3709,6 +3713,31 @@ size_t stitch_host_smem_bytes(int N, int *th_cap) {
 // =========================================================================================
 // C ABI
 // =========================================================================================
+// the coarse tracker's view of window `win` after a pass (ldso_ct_make_reference_ba)
+int ldso_ba::ba_ref_view(const ldso_ba_ctx *c, int win, ldso_ba::BaRefView *out) {
+    if (!c || !out) return set_error(-1, "null argument");
+    if (win < 0 || win >= c->n_win) return set_error(-1, "window index out of range");
+    const WinDev &D = c->wd[win];
+    out->center = reinterpret_cast<const float *>(c->d_rs_center.p) + D.res_base;
+    out->plane_stride = c->R_tot;
+    out->state = c->d_rs_state.p + D.res_base;
+    out->tgt = c->d_rs_tgt.p + D.res_base;
+    out->slot = c->d_rs_slot.p + D.res_base;
+    out->pt_out = c->d_pt_out.p + (size_t)D.point_base * 12;
+    out->R = D.R;
+    out->P = D.P;
+    out->N = D.N;
+    out->rec_base = D.rec_base;
+    out->width = D.width;
+    out->height = D.height;
+    out->device = c->device;
+    out->stream = (void *)c->stream;
+    out->marg = c->marg;
+    out->sharded = c->comm_world > 1 || c->shard_count > 1;
+    out->have_pass = c->pass_since_load;
+    return 0;
+}
+
 extern "C" {
 
 int ldso_ba_abi_version(void) { return LDSO_BA_ABI_VERSION; }
@@ -3941,6 +3970,8 @@ int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->n_win = n_windows;
+    c->shard_count = shard_count;
+    c->pass_since_load = false;
     c->x_stride = 0;
     c->x_prun = 0;
     c->marg = parent != nullptr;
@@ -4469,6 +4500,7 @@ static int linearize_pass(ldso_ba_ctx *c, int fix, int accumulate, const Switche
     c->sys_host_valid = false;
     c->energy_valid = false;
     c->th_host_valid = false;
+    c->pass_since_load = true;
     const bool in_opt = c->opt_pass >= 0;
     LinParams L = lin_params(c);
     L.fix = fix;
@@ -5092,6 +5124,7 @@ int launch_cached_graph(ldso_ba_ctx *c, ldso_ba_ctx::Graph &g, const std::vector
     c->sys_host_valid = false;
     c->energy_valid = false;
     c->th_host_valid = false;
+    c->pass_since_load = true;
     return 0;
 }
 }  // namespace

@@ -108,6 +108,27 @@ struct CtFrameView {
 };
 int ct_frame_view(const ldso_ct_ctx *ct, CtFrameView *out);
 
+// The mirror image: one window of a BA context as the coarse tracker reads it after a pass
+// (ldso_ct_make_reference_ba; the tracker translation unit does not see ldso_ba_ctx).  Every
+// pointer is device memory already offset to the window.  Residuals are in device order; the
+// window's point q (device order: host frame, then point_rank) owns the residuals whose record
+// slot is rec_base + s * P + q.
+struct BaRefView {
+    const float *center;     // planes x, y, z of centerProjectedTo: center[k * plane_stride + r]
+    long long plane_stride;  // floats between two planes
+    const int8_t *state;     // [R] state_state
+    const uint8_t *tgt;      // [R] target frame
+    const int *slot;         // [R] record slot
+    const float *pt_out;     // [P][12], [0] = HdiF
+    int R, P, N, rec_base;
+    int width, height, device;
+    void *stream;            // hipStream_t every BA kernel runs on
+    bool marg;               // a marginalisation context
+    bool sharded;            // the context holds a shard of its windows' points
+    bool have_pass;          // a linearisation pass has run since the last load
+};
+int ba_ref_view(const ldso_ba_ctx *ba, int win, BaRefView *out);
+
 int frame_precalc(int N, const ldso_ba_frame_state *fr, const float calib[4], float *out);
 int set_adjoints(int N, const ldso_ba_frame_state *fr, double *adH, double *adT, double *cPrior);
 int frame_take_data(int N, const ldso_ba_frame_state *fr, float mode_a, float mode_b, double *prior, double *delta,

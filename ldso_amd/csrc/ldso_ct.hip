@@ -18,6 +18,9 @@
 //   k_ct_calc_gs    thread per point with state "warped": the 8 Jacobian entries + residual of
 //                   calcGSSSE and the 45 weighted outer-product terms of Accumulator9, reduced over
 //                   the wavefront and the block into 45 partials per block.
+// Per keyframe (CoarseTracker::makeCoarseDepthL0, CoarseTracker.cc:357-538), the reference cloud from
+// the window's contributions: k_ct_cd_gather / _scatter / _pyr / _flag / _scan / _write in
+// k_ct_coarse_depth.h, whose opening comment describes them; bit-identical to the CPU restatement.
 // Immature points (ImmaturePoint.cc:14-39, 47-317; FullSystem::traceNewCoarse):
 //   k_ct_make_immature  thread per new point: 8 bilinear pattern samples of the new frame.
 //   k_ct_trace          wavefront per immature point: the scalar preamble (epipolar segment,
@@ -666,6 +669,11 @@ __global__ __launch_bounds__(1024) void k_ct_ip_count(const IpRec *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
+// makeCoarseDepthL0 (CoarseTracker.cc:357-538): the reference cloud built on the device
+// ---------------------------------------------------------------------------------------------
+#include "k_ct_coarse_depth.h"
+
+// ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
 void affine_from_to(float expF, float expT, float aF, float bF, float aT, float bT, float &a, float &b) {
@@ -708,6 +716,17 @@ struct ldso_ct_ctx {
     IpRec *d_mk = nullptr;
     int mk_cap = 0;
     int *d_counts = nullptr, *h_counts = nullptr;
+    // makeCoarseDepthL0 on the device (k_ct_coarse_depth.h): work buffers, allocated on first use;
+    // only the contributions grow
+    float4 *d_cd_contrib = nullptr, *h_cd_contrib = nullptr;  // device / pinned staging
+    int cd_contrib_cap = 0, cd_stage_cap = 0;
+    float *d_cd_maps = nullptr;      // idepth | weightSums, every level flat (2 x pyr.off[levels])
+    float4 *d_cd_cand = nullptr;     // a candidate per pixel of every level
+    int *d_cd_blk = nullptr;         // [blocks] counts, then offsets; [blocks .. +levels] level offsets
+    int *h_cd_counts = nullptr, *d_cd_counts = nullptr;  // mapped: pc_n per level
+    CdLevels cd_lv{};
+    int cd_interior = 0, cd_interior0 = 0;  // interior pixels of all levels / of level 0
+    hipEvent_t cd_ev_a = nullptr, cd_ev_b = nullptr;
     // kernel timing
     bool timing = false;
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
@@ -912,9 +931,203 @@ void finish_calc_gs(ldso_ct_ctx *c, int lvl, const double *parts, double *H_out,
     }
 }
 
+// ---- the reference cloud built on the device (k_ct_coarse_depth.h) ----------------------------
+template <typename T>
+int cd_grow(ldso_ct_ctx *c, T *&p, int &cap, int n, bool pinned) {
+    if (n <= cap) return 0;
+    if (p) {
+        CT_TRY(hipStreamSynchronize(c->stream));
+        (void)(pinned ? hipHostFree(p) : hipFree(p));
+    }
+    p = nullptr;
+    cap = 0;
+    if (pinned) CT_TRY(hipHostMalloc(&p, (size_t)n * sizeof(T), hipHostMallocDefault));
+    else CT_TRY(hipMalloc(&p, (size_t)n * sizeof(T)));
+    cap = n;
+    return 0;
+}
+
+// the work buffers, whose sizes follow the context's image size: allocated by the first call only.
+// The cloud holds at most the interior pixels of every level, the warped buffers those of level 0.
+int cd_ensure(ldso_ct_ctx *c) {
+    const PyrParams &P = c->pyr;
+    const int npx = P.off[P.levels];
+    if (!c->cd_interior0 && !c->cd_lv.blk_off[P.levels]) {
+        int nb = 0;
+        for (int l = 0; l <= LDSO_CT_MAX_LEVELS; l++) {
+            c->cd_lv.blk_off[l] = nb;
+            if (l >= P.levels) continue;
+            nb += (P.wl[l] * P.hl[l] + kCtThreads - 1) / kCtThreads;
+            const int in = std::max(0, P.wl[l] - 4) * std::max(0, P.hl[l] - 4);
+            c->cd_interior += in;
+            if (l == 0) c->cd_interior0 = in;
+        }
+    }
+    const int nb = c->cd_lv.blk_off[P.levels];
+    if (!c->d_cd_maps) CT_TRY(hipMalloc(&c->d_cd_maps, 2 * (size_t)npx * sizeof(float)));
+    if (!c->d_cd_cand) CT_TRY(hipMalloc(&c->d_cd_cand, (size_t)npx * sizeof(float4)));
+    if (!c->d_cd_blk) CT_TRY(hipMalloc(&c->d_cd_blk, (size_t)(nb + LDSO_CT_MAX_LEVELS + 1) * sizeof(int)));
+    if (!c->h_cd_counts) {
+        CT_TRY(hipHostMalloc(&c->h_cd_counts, LDSO_CT_MAX_LEVELS * sizeof(int),
+                             hipHostMallocCoherent | hipHostMallocMapped));
+        void *d = nullptr;
+        CT_TRY(hipHostGetDevicePointer(&d, c->h_cd_counts, 0));
+        c->d_cd_counts = static_cast<int *>(d);
+    }
+    if (!c->cd_ev_a) CT_TRY(hipEventCreateWithFlags(&c->cd_ev_a, hipEventDisableTiming));
+    if (!c->cd_ev_b) CT_TRY(hipEventCreateWithFlags(&c->cd_ev_b, hipEventDisableTiming));
+    int rc = cd_grow(c, c->d_pc, c->pc_cap, std::max(1, c->cd_interior), false);
+    if (rc) return rc;
+    if (c->cd_interior0 > c->warp_cap) {
+        CT_TRY(hipStreamSynchronize(c->stream));
+        if (c->d_state) (void)hipFree(c->d_state);
+        if (c->d_warp) (void)hipFree(c->d_warp);
+        c->d_state = nullptr;
+        c->d_warp = nullptr;
+        c->warp_cap = 0;
+        CT_TRY(hipMalloc(&c->d_state, (size_t)c->cd_interior0));
+        CT_TRY(hipMalloc(&c->d_warp, (size_t)c->cd_interior0 * 2 * sizeof(float4)));
+        c->warp_cap = c->cd_interior0;
+    }
+    return 0;
+}
+
+// the checks both make calls share, before any HIP call; *src = the context whose frame is read
+int cd_check(ldso_ct_ctx *c, const ldso_ct_ctx *frame_src, const ldso_ct_ctx **src) {
+    if (!c) return set_error(-1, "null context");
+    const ldso_ct_ctx *s = frame_src ? frame_src : c;
+    if (s->device != c->device) return set_error(-1, "frame_src is on a different device");
+    if (s->pyr.w != c->pyr.w || s->pyr.h != c->pyr.h) return set_error(-1, "frame_src has a different image size");
+    if (!s->have_frame) return set_error(-1, "ldso_ct_set_new_frame has not been called on the frame source");
+    *src = s;
+    return 0;
+}
+
+// from n contributions in d_cd_contrib to the resident cloud: maps, pyramid, dilation, compaction,
+// one synchronisation for the per-level counts
+int cd_build(ldso_ct_ctx *c, const ldso_ct_ctx *src, int n, double ref_ab_exposure, double ref_aff_a, double ref_aff_b,
+             int32_t *pc_n_out) {
+    const PyrParams &P = c->pyr;
+    const int npx = P.off[P.levels], nb = c->cd_lv.blk_off[P.levels];
+    const size_t px0 = (size_t)P.w * P.h;
+    float *idm = c->d_cd_maps, *wm = idm + npx;
+    int *blk = c->d_cd_blk, *lvl_off = blk + nb;
+    // level 0 of both maps is summed into; the coarser levels are written whole
+    CT_TRY(hipMemsetAsync(idm, 0, px0 * sizeof(float), c->stream));
+    CT_TRY(hipMemsetAsync(wm, 0, px0 * sizeof(float), c->stream));
+    if (n > 0)
+        k_ct_cd_scatter<<<(n + kCtThreads - 1) / kCtThreads, kCtThreads, 0, c->stream>>>(c->d_cd_contrib, n, idm, wm,
+                                                                                        P.w, P.h);
+    if (P.levels > 1) {
+        const size_t lds = 2 * ((size_t)P.tile * P.tile + (size_t)(P.tile / 2) * (P.tile / 2)) * sizeof(float);
+        k_ct_cd_pyr<<<dim3(P.w / P.tile, P.h / P.tile), kCtThreads, lds, c->stream>>>(idm, wm, P);
+    }
+    // the colours come from the frame source's pyramid: wait for what its stream holds now, and
+    // let whatever it is given later (its next frame) wait for the read
+    if (src != c) {
+        CT_TRY(hipEventRecord(c->cd_ev_a, src->stream));
+        CT_TRY(hipStreamWaitEvent(c->stream, c->cd_ev_a, 0));
+    }
+    k_ct_cd_flag<<<nb, kCtThreads, 0, c->stream>>>(idm, wm, src->d_dIp, c->d_cd_cand, blk, P, c->cd_lv);
+    if (src != c) {
+        CT_TRY(hipEventRecord(c->cd_ev_b, c->stream));
+        CT_TRY(hipStreamWaitEvent(src->stream, c->cd_ev_b, 0));
+    }
+    k_ct_cd_scan<<<1, kCtThreads, 0, c->stream>>>(blk, lvl_off, c->d_cd_counts, P.levels, c->cd_lv);
+    k_ct_cd_write<<<nb, kCtThreads, 0, c->stream>>>(c->d_cd_cand, blk, lvl_off, c->d_pc, P, c->cd_lv);
+    CT_TRY(hipGetLastError());
+    c->have_ref = false;  // until the counts are in
+    CT_TRY(hipStreamSynchronize(c->stream));
+    int off = 0;
+    for (int l = 0; l < c->levels; l++) {
+        c->pc_off[l] = off;
+        off += c->h_cd_counts[l];
+        if (pc_n_out) pc_n_out[l] = c->h_cd_counts[l];
+    }
+    c->pc_off[c->levels] = off;
+    c->ref_exposure = (float)ref_ab_exposure;
+    c->ref_a = (float)ref_aff_a;
+    c->ref_b = (float)ref_aff_b;
+    c->have_ref = true;
+    c->last_lvl = -1;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int ldso_ct_make_reference(ldso_ct_ctx *c, const ldso_ct_ctx *frame_src, int32_t n, const float *center,
+                           const float *hdi, double ref_ab_exposure, double ref_aff_a, double ref_aff_b,
+                           int32_t *pc_n_out) {
+    const ldso_ct_ctx *src = nullptr;
+    int rc = cd_check(c, frame_src, &src);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!center || !hdi))) return set_error(-1, "bad contribution arguments");
+    CT_TRY(hipSetDevice(c->device));
+    if ((rc = cd_ensure(c))) return rc;
+    if (n > 0) {
+        if ((rc = cd_grow(c, c->d_cd_contrib, c->cd_contrib_cap, n, false))) return rc;
+        if ((rc = cd_grow(c, c->h_cd_contrib, c->cd_stage_cap, n, true))) return rc;
+        // (the staging buffer is free: every call that copies out of it ends with a synchronisation)
+        for (int i = 0; i < n; i++)
+            c->h_cd_contrib[i] = make_float4(center[3 * (size_t)i], center[3 * (size_t)i + 1], center[3 * (size_t)i + 2], hdi[i]);
+        CT_TRY(hipMemcpyAsync(c->d_cd_contrib, c->h_cd_contrib, (size_t)n * sizeof(float4), hipMemcpyHostToDevice,
+                              c->stream));
+    }
+    return cd_build(c, src, n, ref_ab_exposure, ref_aff_a, ref_aff_b, pc_n_out);
+}
+
+int ldso_ct_make_reference_ba(ldso_ct_ctx *c, const ldso_ct_ctx *frame_src, const ldso_ba_ctx *ba, int32_t win,
+                              int32_t ref_frame, double ref_ab_exposure, double ref_aff_a, double ref_aff_b,
+                              int32_t *pc_n_out) {
+    const ldso_ct_ctx *src = nullptr;
+    int rc = cd_check(c, frame_src, &src);
+    if (rc) return rc;
+    if (!ba) return set_error(-1, "null bundle-adjustment context");
+    ldso_ba::BaRefView V;
+    if ((rc = ldso_ba::ba_ref_view(ba, win, &V))) return rc;
+    if (V.device != c->device) return set_error(-1, "the bundle-adjustment context is on a different device");
+    if (V.marg) return set_error(-1, "a marginalisation context holds no tracking reference");
+    if (V.sharded) return set_error(-1, "the context holds a shard of its points: the reference needs the whole window");
+    if (!V.have_pass) return set_error(-1, "no linearisation pass has run since the context's last load");
+    if (ref_frame < -1 || ref_frame >= V.N) return set_error(-1, "ref_frame out of range");
+    if (V.width != c->pyr.w || V.height != c->pyr.h)
+        return set_error(-1, "the tracker's frame size differs from the window's images");
+    if (ref_frame < 0) ref_frame = V.N - 1;
+    CT_TRY(hipSetDevice(c->device));
+    if ((rc = cd_ensure(c))) return rc;
+    const int n = V.R > 0 ? V.P : 0;
+    if (n > 0) {
+        if ((rc = cd_grow(c, c->d_cd_contrib, c->cd_contrib_cap, n, false))) return rc;
+        // read the pass's arrays behind what the BA stream holds now; its later work waits for the read
+        hipStream_t bs = static_cast<hipStream_t>(V.stream);
+        CT_TRY(hipEventRecord(c->cd_ev_a, bs));
+        CT_TRY(hipStreamWaitEvent(c->stream, c->cd_ev_a, 0));
+        CT_TRY(hipMemsetAsync(c->d_cd_contrib, 0xFF, (size_t)n * sizeof(float4), c->stream));  // NaN: no contribution
+        CdGatherParams G{V.center, V.plane_stride, V.state, V.tgt, V.slot, V.pt_out, c->d_cd_contrib,
+                         V.R,      V.P,            V.rec_base, ref_frame};
+        k_ct_cd_gather<<<(V.R + kCtThreads - 1) / kCtThreads, kCtThreads, 0, c->stream>>>(G);
+        CT_TRY(hipGetLastError());
+        CT_TRY(hipEventRecord(c->cd_ev_b, c->stream));
+        CT_TRY(hipStreamWaitEvent(bs, c->cd_ev_b, 0));
+    }
+    return cd_build(c, src, n, ref_ab_exposure, ref_aff_a, ref_aff_b, pc_n_out);
+}
+
+int ldso_ct_get_reference(ldso_ct_ctx *c, int32_t lvl, int32_t *n_out, float *out, int32_t capacity) {
+    if (!c || !n_out) return set_error(-1, "null argument");
+    if (lvl < 0 || lvl >= c->levels) return set_error(-1, "pyramid level out of range");
+    if (!c->have_ref) return set_error(-1, "no reference: call ldso_ct_set_reference or ldso_ct_make_reference first");
+    const int n = c->pc_off[lvl + 1] - c->pc_off[lvl];
+    *n_out = n;
+    if (!out || n == 0) return 0;
+    if (capacity < n) return set_error(-1, "capacity below the level's point count");
+    CT_TRY(hipSetDevice(c->device));
+    CT_TRY(hipMemcpyAsync(out, c->d_pc + c->pc_off[lvl], (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    CT_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
 
 int ldso_ct_create(int32_t device, int32_t width, int32_t height, ldso_ct_ctx **out, int32_t *n_levels_out) {
     if (!out) return set_error(-1, "null output pointer");
@@ -975,9 +1188,14 @@ void ldso_ct_destroy(ldso_ct_ctx *c) {
         (void)hipEventDestroy(p.second.second);
     }
     void *dev[] = {c->d_color, c->d_inten, c->d_B,  c->d_dIp, c->d_pc,  c->d_state,  c->d_warp,
-                   c->d_poses, c->d_ip, c->d_hosts, c->d_uv, c->d_mk, c->d_counts};
+                   c->d_poses, c->d_ip, c->d_hosts, c->d_uv, c->d_mk, c->d_counts,
+                   c->d_cd_contrib, c->d_cd_maps, c->d_cd_cand, c->d_cd_blk};
     for (void *p : dev)
         if (p) (void)hipFree(p);
+    if (c->h_cd_contrib) (void)hipHostFree(c->h_cd_contrib);
+    if (c->h_cd_counts) (void)hipHostFree(c->h_cd_counts);
+    if (c->cd_ev_a) (void)hipEventDestroy(c->cd_ev_a);
+    if (c->cd_ev_b) (void)hipEventDestroy(c->cd_ev_b);
     if (c->h_poses) (void)hipHostFree(c->h_poses);
     if (c->h_hosts) (void)hipHostFree(c->h_hosts);
     if (c->h_counts) (void)hipHostFree(c->h_counts);

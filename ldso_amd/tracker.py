@@ -6,6 +6,9 @@ Mirrors the reference class (src/frontend/CoarseTracker.cc) for the parts that r
     makeK(HCalib)                         -> make_k(calib)                     CoarseTracker.cc:312-339
     newFrame->makeImages(color, HCalib)   -> set_new_frame(color, exposure)    FrameHessian.cc:59-115
     setCoarseTrackingRef's pc_* outputs   -> set_reference(levels, ...)        CoarseTracker.cc:357-538
+    makeCoarseDepthL0 on the device       -> make_reference(center, hdi, ...)  CoarseTracker.cc:357-538
+                                             make_reference_from(ba_ctx, win)  FullSystem.cc:613-621
+                                             reference(lvl) reads the cloud back
     calcRes(lvl, refToNew, aff, cutoff)   -> calc_res(lvl, T, aff, cutoff)     CoarseTracker.cc:540-673
     calcGSSSE(lvl, H, b, refToNew, aff)   -> calc_gs(lvl, T, aff)              CoarseTracker.cc:675-741
     calcRes + calcGSSSE at one pose       -> calc_res_gs(lvl, T, aff, cutoff)  CoarseTracker.cc:90-105, 218-245
@@ -86,6 +89,38 @@ class CoarseTracker:
                 arrs[j][l] = L.ptr(cols[j], L.f32p)
         L.check(L.lib().ldso_ct_set_reference(self._h, L.ptr(n, L.i32p), *arrs, float(ab_exposure),
                                               float(aff_ab[0]), float(aff_ab[1])))
+
+    def make_reference(self, center, hdi, ab_exposure: float = 1.0, aff_ab=(0.0, 0.0), frame_src=None) -> np.ndarray:
+        """makeCoarseDepthL0 on the device from contributions in traversal order: center [n][3]
+        (centerProjectedTo), hdi [n] (HdiF).  frame_src: the tracker whose new frame is the reference
+        keyframe (None: this one).  Returns pc_n per level."""
+        center = _f32(center).reshape(-1, 3)
+        hdi = _f32(hdi).reshape(-1)
+        assert center.shape[0] == hdi.size
+        n = np.zeros(self.levels, np.int32)
+        L.check(L.lib().ldso_ct_make_reference(self._h, None if frame_src is None else frame_src._h, int(hdi.size),
+                                               L.ptr(center, L.f32p), L.ptr(hdi, L.f32p), float(ab_exposure),
+                                               float(aff_ab[0]), float(aff_ab[1]), L.ptr(n, L.i32p)))
+        return n
+
+    def make_reference_from(self, ba_ctx, win: int, ref_frame: int = -1, frame_src=None, ab_exposure: float = 1.0,
+                            aff_ab=(0.0, 0.0)) -> np.ndarray:
+        """The same from the last pass of a BAContext's window, device to device (ref_frame -1: the
+        window's last frame).  Returns pc_n per level."""
+        n = np.zeros(self.levels, np.int32)
+        L.check(L.lib().ldso_ct_make_reference_ba(self._h, None if frame_src is None else frame_src._h, ba_ctx._h,
+                                                  int(win), int(ref_frame), float(ab_exposure), float(aff_ab[0]),
+                                                  float(aff_ab[1]), L.ptr(n, L.i32p)))
+        return n
+
+    def reference(self, lvl: int) -> np.ndarray:
+        """The resident cloud of level lvl as [n][4] {u, v, idepth, color}."""
+        n = C.c_int32()
+        lib = L.lib()
+        L.check(lib.ldso_ct_get_reference(self._h, int(lvl), C.byref(n), L.ptr(None, L.f32p), 0))
+        out = np.zeros((n.value, 4), np.float32)
+        L.check(lib.ldso_ct_get_reference(self._h, int(lvl), C.byref(n), L.ptr(out, L.f32p), int(n.value)))
+        return out
 
     def calc_res(self, lvl: int, ref_to_new, aff_ab=(0.0, 0.0), cutoff_th: float = 20.0) -> np.ndarray:
         T = np.ascontiguousarray(np.asarray(ref_to_new, np.float64)[:3, :4])

@@ -1,0 +1,279 @@
+"""The tracker's reference cloud built on the device (ldso_ct_make_reference from host
+contributions, ldso_ct_make_reference_ba from a bundle-adjustment context's last pass) against the
+numpy restatement of CoarseTracker::makeCoarseDepthL0 in tests/coarse_depth_ref.py.  Every
+comparison is byte-exact on (u, v, idepth, color) per level, counts included."""
+import numpy as np
+import pytest
+
+import coarse_depth_ref as R
+from ldso_amd import _lib as L
+from ldso_amd import dist as ldist
+from ldso_amd import synth
+
+F = np.float32
+pytestmark = pytest.mark.gpu
+AFF_REF, AFF_NEW = (0.02, 1.5), (0.05, -0.8)
+
+
+def _tracker(w, h, color=None, seed=4):
+    from ldso_amd.tracker import CoarseTracker
+
+    if color is None:
+        color, _ = synth.make_tracker_scene(w, h, seed=seed)
+    ct = CoarseTracker(w, h)
+    ct.make_k(np.array([0.6 * w, 0.9 * h, 0.5 * w - 0.5, 0.5 * h - 0.5], F))
+    ct.set_new_frame(color, 1.0)
+    return ct
+
+
+def _colors(ct):
+    return [np.ascontiguousarray(ct.frame_level(l)[0][:, 0]) for l in range(ct.levels)]
+
+
+def _clouds(ct):
+    return [ct.reference(l) for l in range(ct.levels)]
+
+
+def _assert_same(got, want, pc_n=None):
+    assert len(got) == len(want)
+    for l, (g, e) in enumerate(zip(got, want)):
+        assert g.shape == e.shape, (l, g.shape, e.shape)
+        assert g.tobytes() == e.tobytes(), (l, int(np.count_nonzero(g.view(np.uint32) != e.view(np.uint32))))
+        if pc_n is not None:
+            assert pc_n[l] == e.shape[0]
+
+
+def _crafted(w, h):
+    """Contributions that exercise every clause of the contract at w x h (3 levels), and the
+    positions of the frame pixels to set to NaN."""
+    c, hd = [R.FIVE_CENTER], [R.FIVE_HDI]  # a five-fold pixel, weights 1e-3 ... 1e3
+    # three-fold at the interior edge x = 2
+    c.append(np.array([[2.1, 100.2, 0.9], [1.8, 99.9, 1.7], [2.4, 100.4, 0.3]], F))
+    hd.append(np.array([1e-2, 3e1, 1e-6], F))
+    # x < 2 and y >= h - 2: they feed the coarser levels, never emitted themselves
+    c.append(np.array([[0.3, 50.0, 0.8], [1.2, 120.0, 1.1], [150.0, h - 1.4, 0.7], [151.0, h - 2.0, 1.9],
+                       [-0.7, -0.7, 1.3]], F))
+    hd.append(np.array([1e-1, 1.0, 10.0, 1e-3, 1e-2], F))
+    # centres outside the image (skipped), one of them NaN
+    c.append(np.array([[-2.0, 10.0, 1.0], [w, 10.0, 1.0], [10.0, -1.6, 1.0], [10.0, h + 0.2, 1.0], [1e9, 5.0, 1.0],
+                       [np.nan, 5.0, 1.0], [w - 0.5, 20.0, 1.0], [30.0, -1e30, 1.0]], F))
+    hd.append(np.full(8, 1e-2, F))
+    # c[2] <= 0 and NaN, alone on a pixel and next to a good contribution on the same pixel
+    c.append(np.array([[200.0, 50.0, -0.5], [210.0, 50.0, 0.0], [220.0, 50.0, np.nan], [230.0, 50.0, 1.0],
+                       [230.2, 50.1, np.nan], [240.0, 50.0, 1.0], [240.2, 49.9, -3.0]], F))
+    hd.append(np.array([1e-2, 1e-2, 1e-2, 1e-2, 1e-1, 1e-2, 1e-1], F))
+    # HdiF from 0 to 1e6 over many magnitudes: the double quotient and sqrtf
+    mags = np.array([0.0, 1e-12, 3e-12, 1e-10, 7e-9, 1e-7, 3.3e-6, 1e-4, 2.5e-3, 0.1, 1.0, 17.0, 1e3, 4.2e4, 1e6], F)
+    xs = 20.0 + 6.0 * np.arange(mags.size)
+    c.append(np.stack([xs, np.full_like(xs, 150.0), np.linspace(0.2, 2.4, mags.size)], axis=1).astype(F))
+    hd.append(mags)
+    # a few hundred ordinary ones, so that the dilations of neighbours interact on every level
+    rng = np.random.default_rng(11)
+    n = 400
+    c.append(np.stack([rng.uniform(-1, w, n), rng.uniform(-1, h, n), rng.uniform(0.1, 2.0, n)], axis=1).astype(F))
+    hd.append((10.0 ** rng.uniform(-6, 4, n)).astype(F))
+    # NaN frame pixels: under a contribution, under a dilated neighbour, under a level-1 parent
+    nan_px = [(20 + 6 * 3, 150), (20 + 6 * 5 + 1, 151), (20 + 6 * 7, 150), (100, 200), (101, 200), (100, 201), (101, 201)]
+    return np.concatenate(c), np.concatenate(hd), nan_px
+
+
+def _pose(i, scale=1.0):
+    om = 0.004 * np.array([np.sin(i), np.cos(2 * i), np.sin(3 * i + 1)])
+    up = 0.03 * scale * np.array([np.cos(i), np.sin(2 * i + 1), 0.3 * np.cos(3 * i)])
+    return synth.se3_matrix(om, up)
+
+
+def test_crafted_contributions(built):
+    w, h = 320, 240
+    center, hdi, nan_px = _crafted(w, h)
+    color, _ = synth.make_tracker_scene(w, h, seed=4)
+    color = color.copy()
+    for x, y in nan_px:
+        color[y, x] = np.nan
+    ct = _tracker(w, h, color)
+    assert ct.levels == 3
+    pc_n = ct.make_reference(center, hdi, 1.0, AFF_REF)
+    want = R.make_coarse_depth(w, h, center, hdi, _colors(ct))
+    _assert_same(_clouds(ct), want, pc_n)
+    # the cases are really in the input: dilation ran, a point was dropped for its colour
+    assert pc_n[0] > center.shape[0] and all(n > 0 for n in pc_n)
+    finite = R.make_coarse_depth(w, h, center, hdi, [np.where(np.isfinite(c), c, F(1)) for c in _colors(ct)])
+    assert finite[0].shape[0] > want[0].shape[0]
+    # the order of the sums matters to this input
+    rev = R.make_coarse_depth(w, h, center[::-1], hdi[::-1], _colors(ct))
+    assert rev[0].tobytes() != want[0].tobytes()
+    # repeatability: a second call gives identical bytes
+    again = ct.make_reference(center, hdi, 1.0, AFF_REF)
+    assert np.array_equal(again, pc_n)
+    _assert_same(_clouds(ct), want)
+    ct.close()
+
+
+def test_no_contributions(built):
+    w, h = 320, 240
+    ct = _tracker(w, h)
+    pc_n = ct.make_reference(np.zeros((0, 3), F), np.zeros(0, F), 1.0, AFF_REF)
+    assert pc_n.tolist() == [0, 0, 0]
+    for l in range(ct.levels):
+        assert ct.reference(l).shape == (0, 4)
+        rs = ct.calc_res(l, _pose(1), AFF_NEW, 20.0)
+        assert rs[1] == 0 and np.isnan(rs[5]) and ct.warped().shape[0] == 0
+        ct.calc_gs(l, _pose(1), AFF_NEW)
+    ct.close()
+
+
+def _random_contributions(w, h, seed, n=2000, clusters=40):
+    """About n contributions, `clusters` pixels with three of them each."""
+    rng = np.random.default_rng(seed)
+    m = n - 3 * clusters
+    c = [np.stack([rng.uniform(-1, w, m), rng.uniform(-1, h, m)], axis=1)]
+    px = np.stack([rng.integers(2, w - 2, clusters), rng.integers(2, h - 2, clusters)], axis=1)
+    for _ in range(3):
+        c.append(px + rng.uniform(-0.45, 0.45, px.shape))
+    xy = np.concatenate(c)
+    perm = rng.permutation(xy.shape[0])  # the partners of a pixel far apart in the order
+    xy = xy[perm]
+    center = np.concatenate([xy, rng.uniform(0.1, 2.0, (xy.shape[0], 1))], axis=1).astype(F)
+    hdi = (10.0 ** rng.uniform(-6, 4, xy.shape[0])).astype(F)
+    return center, hdi
+
+
+@pytest.mark.parametrize("wh,levels", [((332, 244), 3), ((322, 242), 2), ((640, 480), 4)])
+def test_sizes(built, wh, levels):
+    w, h = wh
+    center, hdi = _random_contributions(w, h, seed=w)
+    count = {}
+    for c in center:
+        p = R.pixel_of(c[0], c[1], w, h)
+        count[p] = count.get(p, 0) + 1
+    assert sum(1 for p, k in count.items() if p is not None and k >= 3) >= 20
+    ct = _tracker(w, h)
+    assert ct.levels == levels
+    pc_n = ct.make_reference(center, hdi, 1.0, AFF_REF)
+    _assert_same(_clouds(ct), R.make_coarse_depth(w, h, center, hdi, _colors(ct)), pc_n)
+    ct.close()
+
+
+def test_tracker_uses_the_device_built_reference(built):
+    w, h = 320, 240
+    center, hdi = _random_contributions(w, h, seed=5)
+    ct = _tracker(w, h)
+    ct.make_reference(center, hdi, 0.9, AFF_REF)
+    dev = [ct.calc_res_gs(l, _pose(l + 1, 2.0 ** l), AFF_NEW, 20.0) for l in range(ct.levels)]
+    assert all(r[0][1] > 100 for r in dev)  # residuals were evaluated
+    ct.set_reference([tuple(np.ascontiguousarray(p[:, k]) for k in range(4)) for p in _clouds(ct)], 0.9, AFF_REF)
+    for l in range(ct.levels):
+        rs, H, b = ct.calc_res_gs(l, _pose(l + 1, 2.0 ** l), AFF_NEW, 20.0)
+        assert rs.tobytes() == dev[l][0].tobytes()
+        assert H.tobytes() == dev[l][1].tobytes() and b.tobytes() == dev[l][2].tobytes()
+    ct.close()
+
+
+def test_frame_src_from_a_second_context(built):
+    w, h = 320, 240
+    center, hdi = _random_contributions(w, h, seed=6, n=600, clusters=10)
+    color, _ = synth.make_tracker_scene(w, h, seed=8)
+    ct = _tracker(w, h, seed=4)      # its own frame is another image
+    kf = _tracker(w, h, color)       # coarseTracker_forNewKF's frame: the reference keyframe
+    ct.make_reference(center, hdi, 1.0, AFF_REF, frame_src=kf)
+    got = _clouds(ct)
+    _assert_same(got, R.make_coarse_depth(w, h, center, hdi, _colors(kf)))
+    ct.set_new_frame(color, 1.0)
+    ct.make_reference(center, hdi, 1.0, AFF_REF)
+    _assert_same(_clouds(ct), got)
+    small = _tracker(160, 120)
+    with pytest.raises(L.LdsoError, match="size"):
+        ct.make_reference(center, hdi, frame_src=small)
+    for t in (ct, kf, small):
+        t.close()
+
+
+# ---- from a bundle-adjustment context ---------------------------------------------------------
+def _ba_windows():
+    other = synth.make_window(n_frames=6, n_points=400, width=320, height=240, seed=3)
+    win = synth.make_window(n_frames=5, n_points=600, width=320, height=240)
+    win.point_rank = np.arange(win.n_points, dtype=np.int32)  # the caller's order, said explicitly
+    return other, win
+
+
+def _run_pass(ctx, kind, windows):
+    if kind == "linearize":
+        ctx.linearize(fix=False, accumulate=True)
+    else:
+        ctx.optimize(3, nullspaces=[w.nullspaces() for w in windows])
+
+
+def _expected_from(ctx, win, ct, ref_frame):
+    res, pts = ctx.residuals(1), ctx.points(1)
+    center, hdi = R.window_contributions(win, res["state"], res["center"], pts["HdiF"], ref_frame)
+    return center.shape[0], R.make_coarse_depth(win.width, win.height, center, hdi, _colors(ct))
+
+
+@pytest.mark.parametrize("kind", ["linearize", "optimize"])
+def test_from_ba_context(built, kind):
+    from ldso_amd import BAContext
+
+    other, win = _ba_windows()
+    ct = _tracker(320, 240)
+    ctx = BAContext(0).load([other, win])
+    _run_pass(ctx, kind, [other, win])
+    pc_n = ct.make_reference_from(ctx, 1, -1, None, 1.0, AFF_REF)
+    got = _clouds(ct)
+    n_in, want = _expected_from(ctx, win, ct, win.n_frames - 1)
+    assert n_in >= 200 and pc_n[0] > n_in  # enough contributions, and the dilation ran
+    _assert_same(got, want, pc_n)
+    # repeatability
+    assert np.array_equal(ct.make_reference_from(ctx, 1, -1, None, 1.0, AFF_REF), pc_n)
+    _assert_same(_clouds(ct), got)
+    # a middle frame as the reference
+    pc_mid = ct.make_reference_from(ctx, 1, 2, None, 1.0, AFF_REF)
+    n_mid, want_mid = _expected_from(ctx, win, ct, 2)
+    assert n_mid >= 200
+    _assert_same(_clouds(ct), want_mid, pc_mid)
+    ctx.close()
+    # the same window with its points permuted and their ranks kept: the same cloud
+    perm = synth.permute_points(win, np.random.default_rng(2).permutation(win.n_points))
+    ctx = BAContext(0).load([other, perm])
+    _run_pass(ctx, kind, [other, perm])
+    pc_p = ct.make_reference_from(ctx, 1, -1, None, 1.0, AFF_REF)
+    _assert_same(_clouds(ct), got, pc_p)
+    n_p, want_p = _expected_from(ctx, perm, ct, perm.n_frames - 1)
+    assert n_p == n_in
+    _assert_same(got, want_p)
+    ctx.close()
+    ct.close()
+
+
+def test_refusals(built):
+    from ldso_amd import BAContext
+
+    other, win = _ba_windows()
+    ct = _tracker(320, 240)
+    ctx = BAContext(0).load([other, win])
+    with pytest.raises(L.LdsoError, match="pass"):  # nothing has run since the load
+        ct.make_reference_from(ctx, 1)
+    ctx.linearize()
+    ct.make_reference_from(ctx, 1)
+    for bad in (win.n_frames, -2):
+        with pytest.raises(L.LdsoError, match="ref_frame"):
+            ct.make_reference_from(ctx, 1, bad)
+    with pytest.raises(L.LdsoError, match="window"):
+        ct.make_reference_from(ctx, 2)
+    big = _tracker(640, 480)
+    with pytest.raises(L.LdsoError, match="size"):
+        big.make_reference_from(ctx, 1)
+    marg = BAContext(0).load_marginalization(ctx, 0, ldist.subset_window(other, np.arange(0, other.n_points, 5)))
+    with pytest.raises(L.LdsoError, match="marginalisation"):
+        ct.make_reference_from(marg, 0)
+    marg.close()
+    shard = BAContext(0).load([win], 0, 2)
+    shard.linearize()
+    with pytest.raises(L.LdsoError, match="shard"):
+        ct.make_reference_from(shard, 0)
+    ctx.load([other, win])  # a reload invalidates the pass
+    with pytest.raises(L.LdsoError, match="pass"):
+        ct.make_reference_from(ctx, 1)
+    for c in (shard, ctx):
+        c.close()
+    ct.close()
+    big.close()
