@@ -92,7 +92,10 @@ typedef struct ldso_ba_window {
     const int32_t *point_res_begin;/* [P+1]: residuals of point p are [begin[p], begin[p+1]) */
     const int32_t *res_target;     /* [R]: target frame index (PointFrameResidual::targetIDX)*/
     const int8_t *res_state;       /* [R]: state_state                                       */
-    const float *res_energy;       /* [R]: state_energy                                      */
+    const float *res_energy;       /* [R]: state_energy; state_NewEnergy is loaded equal to it, as
+                                    * the reference leaves the two between keyframe cycles (a
+                                    * residual that then goes OOB gets it back as state_energy);
+                                    * ldso_ba_update_residuals sets them apart              */
     const uint8_t *res_flags;      /* [R]: LDSO_BA_FLAG_*                                    */
     /* [P] or NULL: the point's rank among its host frame's points in the order of the host
      * Frame's features vector.  The library keeps each host's points in this order (NULL: the

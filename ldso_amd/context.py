@@ -229,6 +229,35 @@ class BAContext:
         v = np.ascontiguousarray(vals, np.float32).reshape(-1, 4)
         L.check(self._lib.ldso_ba_update_points(self._h, int(win), L.ptr(v, L.f32p)))
 
+    def update_residuals(self, win: int, state, state_energy, new_energy, flags):
+        """ldso_ba_update_residuals: residual states edited on the host (resetOOB / applyRes / setState)
+        into the device mirror of window `win`, [R] each in the caller's residual order: state_state,
+        state_energy, state_NewEnergy, flags (L.FLAG_*)."""
+        L.check(self._lib.ldso_ba_update_residuals(
+            self._h, int(win), L.ptr(np.ascontiguousarray(state, np.int8), L.i8p),
+            L.ptr(np.ascontiguousarray(state_energy, np.float32), L.f32p),
+            L.ptr(np.ascontiguousarray(new_energy, np.float32), L.f32p),
+            L.ptr(np.ascontiguousarray(flags, np.uint8), L.u8p)))
+
+    def linearize_residuals(self, win: int, only=None) -> dict:
+        """ldso_ba_linearize_residuals: PointFrameResidual::linearize of every residual of window
+        `win` as right after its resetOOB, on scratch copies (the context's states, records and
+        system stay as they were) -> new_state, new_energy, new_energy_wo, center [R][3], center_ok,
+        jpjdf [R][8] in the caller's residual order.  only: the outputs to request (the others are
+        passed as NULL and left out of the result); None = all."""
+        if not 0 <= win < len(self.windows):  # refused by the library, with its message
+            L.check(self._lib.ldso_ba_linearize_residuals(self._h, int(win), None, None, None, None, None, None))
+        R = self.windows[win].n_residuals
+        o = dict(new_state=np.zeros(R, np.int8), new_energy=np.zeros(R, np.float32),
+                 new_energy_wo=np.zeros(R, np.float32), center=np.zeros((R, 3), np.float32),
+                 center_ok=np.zeros(R, np.uint8), jpjdf=np.zeros((R, 8), np.float32))
+        if only is not None:
+            o = {k: v for k, v in o.items() if k in only}
+        types = dict(new_state=L.i8p, new_energy=L.f32p, new_energy_wo=L.f32p, center=L.f32p, center_ok=L.u8p,
+                     jpjdf=L.f32p)
+        L.check(self._lib.ldso_ba_linearize_residuals(self._h, int(win), *[L.ptr(o.get(k), t) for k, t in types.items()]))
+        return o
+
     def reset_oob(self, win: int = -1):
         L.check(self._lib.ldso_ba_reset_oob(self._h, int(win)))
 

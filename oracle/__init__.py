@@ -49,6 +49,7 @@ def lib():
             "oracle_reset_oob": (None, [C.c_void_p]),
             "oracle_linearize_all": (C.c_int, [C.c_void_p, C.c_int, f64p]),
             "oracle_apply_res": (None, [C.c_void_p]),
+            "oracle_set_residuals": (None, [C.c_void_p, i8p, f32p, f32p, u8p]),
             "oracle_accumulate": (C.c_int, [C.c_void_p, f64p, f64p, f64p, f64p, f64p, f64p]),
             "oracle_iteration": (C.c_int, [C.c_void_p, f64p]),
             "oracle_get_residuals": (None, [C.c_void_p, i8p, i8p, f32p, f32p, f32p, u8p, f32p, f32p]),
@@ -139,6 +140,14 @@ class OracleWindow:
 
     def apply_res(self):
         lib().oracle_apply_res(self._h)
+
+    def set_residuals(self, state=None, state_energy=None, new_energy=None, flags=None):
+        """Residual states edited from outside ([R] each, caller order; None leaves a field as it
+        is): state_state, state_energy, state_NewEnergy, flags -- BAContext.update_residuals' twin."""
+        a = [None if x is None else np.ascontiguousarray(x, t) for x, t in
+             ((state, np.int8), (state_energy, np.float32), (new_energy, np.float32), (flags, np.uint8))]
+        assert all(x is None or x.shape == (self.window.n_residuals,) for x in a)
+        lib().oracle_set_residuals(self._h, _p(a[0], i8p), _p(a[1], f32p), _p(a[2], f32p), _p(a[3], u8p))
 
     def accumulate(self) -> dict:
         n = self.window.dim

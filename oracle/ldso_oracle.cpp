@@ -491,6 +491,13 @@ void load_update(oracle_window *ow, const ldso_ba_window *w, bool structure) {
                 r.targetIDX = w->res_target[k];
                 r.state_state = w->res_state[k];
                 r.state_energy = w->res_energy[k];
+                // state_energy is only ever written as state_NewEnergy's copy (applyRes, Residuals.h:87)
+                // or zeroed with it (resetOOB, :64), and every linearize is followed by an applyRes
+                // that either copies or, for an OOB residual, finds state_NewEnergy untouched: between
+                // keyframe cycles the two are equal.  A residual that goes OOB in the next pass gets
+                // this value back as its state_energy (linearize returns before it writes
+                // state_NewEnergy, Residuals.cc:61-62, 133-134, 145-146).
+                r.state_NewEnergy = r.state_energy;
                 r.isActiveAndIsGoodNEW = (w->res_flags[k] & LDSO_BA_FLAG_ACTIVE) != 0;
                 r.isNew = (w->res_flags[k] & LDSO_BA_FLAG_NEW) != 0;
                 std::memset(&r.J, 0, sizeof(r.J));
@@ -1581,6 +1588,20 @@ int oracle_linearize_all(oracle_window *ow, int fix, double *out) {
     return 0;
 }
 void oracle_apply_res(oracle_window *ow) { applyResAll(ow); }
+
+void oracle_set_residuals(oracle_window *ow, const int8_t *state, const float *state_energy,
+                          const float *new_energy, const uint8_t *flags) {
+    for (size_t k = 0; k < ow->res.size(); k++) {
+        Residual &r = ow->res[k];
+        if (state) r.state_state = state[k];
+        if (state_energy) r.state_energy = state_energy[k];
+        if (new_energy) r.state_NewEnergy = new_energy[k];
+        if (flags) {
+            r.isActiveAndIsGoodNEW = (flags[k] & LDSO_BA_FLAG_ACTIVE) != 0;
+            r.isNew = (flags[k] & LDSO_BA_FLAG_NEW) != 0;
+        }
+    }
+}
 
 int oracle_accumulate(oracle_window *ow, double *HA, double *bA, double *HL, double *bL,
                       double *Hsc, double *bsc) {

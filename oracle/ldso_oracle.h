@@ -42,6 +42,10 @@ void oracle_reset_oob(oracle_window *ow);
 int oracle_linearize_all(oracle_window *ow, int fix, double *out);
 /* FullSystem::applyRes_Reductor(true) over all residuals */
 void oracle_apply_res(oracle_window *ow);
+/* residual states edited from outside, as ldso_ba_update_residuals takes them ([R], caller order,
+ * any may be NULL): state_state, state_energy, state_NewEnergy, LDSO_BA_FLAG_* */
+void oracle_set_residuals(oracle_window *ow, const int8_t *state, const float *state_energy,
+                          const float *new_energy, const uint8_t *flags);
 /* accumulateAF_MT + accumulateLF_MT + accumulateSCF_MT (with stitches); any output may be NULL */
 int oracle_accumulate(oracle_window *ow, double *HA, double *bA, double *HL, double *bL,
                       double *Hsc, double *bsc);

@@ -74,27 +74,33 @@ def window(cfg, s):
 
 @pytest.mark.parametrize("case", range(10))
 def test_random_optimize_matches_host_loop(built, case, monkeypatch):
+    cfgs, aff = draw(case)
+    print(f"case {case}: affine {aff}")
+    check_optimize_against_host_loop([(lambda s, c=c: window(c, s)) for c in cfgs], cfgs, aff, case, monkeypatch)
+
+
+def check_optimize_against_host_loop(factories, labels, aff, case, monkeypatch):
+    """factories: one per window of the batch, each f(settings) -> a fresh copy of that window;
+    labels: what to print for each; case: seeds the perturbed host loops."""
     from ldso_amd import BAContext
     from test_optimize import host_optimize
 
-    cfgs, aff = draw(case)
-    print(f"case {case}: affine {aff}")
     s = L.OptSettings.default(affine_opt_mode_a=aff[0], affine_opt_mode_b=aff[1])
-    ws = [window(c, s) for c in cfgs]
+    ws = [f(s) for f in factories]
     nss = [w.nullspaces() for w in ws]
     ctx = BAContext(0).set_settings(s).load(ws)
     e_dev, fr_dev, c_dev, idep_dev, its_dev, st_dev = ctx.optimize(N_ITS, nullspaces=nss)
     ctx.close()
     off = 0
     with oracle.affine_opt_modes(*aff):
-        for i, (cfg, ns) in enumerate(zip(cfgs, nss)):
-            n = cfg["n_frames"]
-            e_h, fr_h, c_h, idep_h, its_h, st_h, ratios = host_optimize(window(cfg, s), N_ITS, ns)
+        for i, (make, cfg, ns) in enumerate(zip(factories, labels, nss)):
+            n = ws[i].n_frames
+            e_h, fr_h, c_h, idep_h, its_h, st_h, ratios = host_optimize(make(s), N_ITS, ns)
             spread_e, spread_fr, spread_id = np.zeros(len(e_h)), 0.0, 0.0
             with monkeypatch.context() as m:
                 for k in range(2):
                     m.setattr(oracle, "solve_system", perturbed_solve(np.random.default_rng(100 * case + k)))
-                    e_p, fr_p, _, idep_p, its_p, _, _ = host_optimize(window(cfg, s), N_ITS, ns)
+                    e_p, fr_p, _, idep_p, its_p, _, _ = host_optimize(make(s), N_ITS, ns)
                     if its_p == its_h:
                         spread_e = np.maximum(spread_e, np.abs(np.array(e_p)[:, 0] - np.array(e_h)[:, 0]))
                         spread_fr = max(spread_fr, float(np.linalg.norm(fr_p["state"] - fr_h["state"])))
@@ -113,7 +119,7 @@ def test_random_optimize_matches_host_loop(built, case, monkeypatch):
                 assert abs(e[p, 0] - e_h[p][0]) <= max(1e-4 * abs(e_h[p][0]), 4 * spread_e[p]), p
                 assert abs(e[p, 2] - e_h[p][2]) <= 2e-3 * e_h[p][2], p
             if (int(its_dev[i]), int(st_dev[i])) == (its_h, st_h) and st_h != L.OPT_LOST:
-                w0 = window(cfg, s)
+                w0 = make(s)
                 fd = fr_dev["state"][off:off + n]
                 assert np.linalg.norm(fd - fr_h["state"]) <= max(0.05 * np.linalg.norm(fr_h["state"] - w0.frames["state"]),
                                                                 4 * spread_fr)

@@ -92,9 +92,6 @@ def test_random_point_marginalisation_matches_oracle(built, case):
     keyframes, the sizes and motions above) with a random subset of points (host 0's and a random
     fraction of the rest) and random linearisation deltas: residual states, JpJdF and the point
     terms bit-exact against the oracle, H / b per 8x8 block within 1e-4 (test_marginalization's bars)."""
-    from ldso_amd import dist as ldist
-    from test_marginalization import ad_ht_delta, block_err, vec_err
-
     rng = np.random.default_rng(7000 + case)
     W, H = SIZES[rng.integers(len(SIZES))]
     cfg = dict(n_frames=int(rng.integers(2, 12)), n_points=int(rng.integers(50, 600)), width=W, height=H,
@@ -103,16 +100,25 @@ def test_random_point_marginalisation_matches_oracle(built, case):
     frac, scale = float(rng.uniform(0.05, 0.5)), float(rng.choice([0.0, 1.0, 3.0]))
     print(f"case {case}: {cfg}, fraction {frac:.2f}, delta scale {scale}")
     w = synth.make_window(**cfg)
-    N = w.n_frames
     S = np.array(sorted(set(np.flatnonzero(w.point_host == 0)) |
                         set(np.flatnonzero(rng.random(w.n_points) < frac))), np.int64)
+    check_point_marginalisation(w, synth.make_window(**cfg), S, scale)
+
+
+def check_point_marginalisation(w, w_oracle, S, scale):
+    """The points S of the parent window w (w_oracle: a second copy of it for the oracle)
+    marginalised on the device against the oracle, with linearisation deltas scaled by `scale`."""
+    from ldso_amd import dist as ldist
+    from test_marginalization import ad_ht_delta, block_err, vec_err
+
+    N = w.n_frames
     adh = ad_ht_delta(w, scale)
     parent = BAContext(0).load([w])
     parent.linearize()
     parent.sync()
     m = BAContext(0).load_marginalization(parent, 0, ldist.subset_window(w, S))
     Hm, bm = m.marginalize_points(adh)
-    ow = oracle.OracleWindow(synth.make_window(**cfg), threads=0)
+    ow = oracle.OracleWindow(w_oracle, threads=0)
     Ho, bo = ow.marginalize_points(S.astype(np.int32), adh)
     assert block_err(Hm, Ho, N) <= 1e-4
     assert vec_err(bm, bo, N) <= 1e-4

@@ -401,3 +401,57 @@ def test_photometric_residuals_known_answer(win):
         np.testing.assert_allclose(Jk["JIdx"], JIdx, rtol=0, atol=jtol * max(np.abs(JIdx).max(), 1e-3))
         np.testing.assert_allclose(Jk["JabF"], JabF, rtol=0, atol=jtol * max(np.abs(JabF).max(), 1e-3))
     assert seen[0] >= 1000 and seen[1] >= 10 and seen[2] >= 10, seen
+
+
+def test_residual_going_oob_keeps_its_loaded_energy():
+    """state_energy across one pass for residuals loaded with a state and a non-zero energy, written
+    from the reference text: linearize returns state_energy at once, before it writes
+    state_NewEnergy, for a residual that is OOB (Residuals.cc:19-22) or leaves the image
+    (:61-62, :133-134, :145-146); applyRes returns early for an OOB residual and otherwise copies
+    state_NewEnergy (Residuals.h:70-88).  state_energy is only ever written as that copy or zeroed
+    together with state_NewEnergy (resetOOB, :64), so a window between keyframe cycles carries
+    state_NewEnergy == state_energy, and:
+      * loaded OOB: stays OOB with the loaded energy;
+      * loaded IN / OUTLIER, goes OOB: the loaded energy again (the copy of an untouched
+        state_NewEnergy) -- or whatever state_NewEnergy was set to from outside -- and 0 after resetOOB;
+      * ends IN: state_NewEnergyWithOutlier of this pass."""
+    cfg = WINDOWS["kitti00_forward"]
+
+    def make():
+        w = synth.make_window(**cfg)
+        k = np.arange(w.n_residuals)
+        w.res_state = np.where(k % 5 == 0, 1, np.where(k % 5 == 1, 2, 0)).astype(np.int8)
+        w.res_energy = (7 + k).astype(np.float32)
+        return w
+
+    w = make()
+    loaded, was_oob = w.res_energy.copy(), w.res_state == 1
+    ow = oracle.OracleWindow(w, threads=0)
+    ow.iteration()
+    r = ow.residuals()
+    went_oob = ~was_oob & (r["state"] == 1)
+    ends_in = r["state"] == 0
+    assert was_oob.sum() >= 100 and went_oob.sum() >= 10 and ends_in.sum() >= 500
+    assert np.all(r["state"][was_oob] == 1)
+    np.testing.assert_array_equal(r["state_energy"][was_oob], loaded[was_oob])
+    np.testing.assert_array_equal(r["state_energy"][went_oob], loaded[went_oob])
+    np.testing.assert_array_equal(r["state_energy"][ends_in], r["new_energy_wo"][ends_in])
+    ow.close()
+    # state_NewEnergy set from outside is what applyRes copies
+    ow = oracle.OracleWindow(make(), threads=0)
+    marks = (1000 + np.arange(w.n_residuals)).astype(np.float32)
+    ow.set_residuals(new_energy=marks)
+    ow.iteration()
+    r2 = ow.residuals()
+    np.testing.assert_array_equal(r2["state"], r["state"])
+    np.testing.assert_array_equal(r2["state_energy"][went_oob], marks[went_oob])
+    np.testing.assert_array_equal(r2["state_energy"][was_oob], loaded[was_oob])
+    ow.close()
+    # after resetOOB both energies are 0: a residual that leaves the image ends with state_energy 0
+    ow = oracle.OracleWindow(make(), threads=0)
+    ow.reset_oob()
+    ow.iteration()
+    r3 = ow.residuals()
+    oob = r3["state"] == 1
+    assert oob.sum() >= 10 and not r3["state_energy"][oob].any()
+    ow.close()

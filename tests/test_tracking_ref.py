@@ -244,6 +244,33 @@ def test_from_ba_context(built, kind):
     ct.close()
 
 
+@pytest.mark.parametrize("ref_frame", [-1, 2])
+def test_from_ragged_ba_window(built, ref_frame):
+    """A window as the frontend leaves it (tests/ragged.py): a point's residual to the reference
+    frame is taken "if it exists" -- here many points have none, the others hold it at any place of
+    a shuffled list, some of those loaded OOB or OUTLIER -- and the points follow their ranks."""
+    import ragged
+    from ldso_amd import BAContext
+
+    other, _ = _ba_windows()
+    win = ragged.frontend_window(synth.make_window(n_frames=7, n_points=900, width=320, height=240, seed=9),
+                                 np.random.default_rng(17000), rank=True)
+    ref = win.n_frames - 1 if ref_frame < 0 else ref_frame
+    has = np.array([ref in win.res_target[win.point_res_begin[p]:win.point_res_begin[p + 1]]
+                    for p in range(win.n_points)])
+    assert np.mean(~has) >= 1 / 3 and has.sum() >= 200
+    ct = _tracker(320, 240)
+    ctx = BAContext(0).load([other, win])
+    for _ in range(2):  # the second pass keeps the OOB states the first one found
+        ctx.linearize(fix=False, accumulate=True)
+    pc_n = ct.make_reference_from(ctx, 1, ref_frame, None, 1.0, AFF_REF)
+    n_in, want = _expected_from(ctx, win, ct, ref)
+    assert n_in >= 100 and pc_n[0] > n_in
+    _assert_same(_clouds(ct), want, pc_n)
+    ctx.close()
+    ct.close()
+
+
 def test_refusals(built):
     from ldso_amd import BAContext
 
