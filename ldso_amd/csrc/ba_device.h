@@ -1,6 +1,6 @@
-// ba_device.h -- what more than one stage of ldso_ba.hip's kernels uses: the window descriptor, the
-// image taps, the centre geometry of a residual record, the wave helpers, the packed-triangle and
-// Top-slot indices, the sumNID chain and the setNewFrameEnergyTH selection.
+// ba_device.h -- what more than one kernel stage (k_*.h) of the ldso_ba.hip unit uses: the window
+// descriptor, the image taps, the centre geometry of a residual record, the wave helpers, the
+// packed-triangle and Top-slot indices, the sumNID chain and the setNewFrameEnergyTH selection.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,8 +8,8 @@
 #include "layout.h"
 #include "ldso_ba_internal.h"
 
-// This header and the k_*.h stage headers are pieces of the one translation unit ldso_ba.hip
-// (anonymous namespace, the using-directive below), not headers for general inclusion.
+// This header, the k_*.h stage headers, ba_context.h and ba_launch.h are pieces of the one translation
+// unit ldso_ba.hip (anonymous namespace, the using-directive below), not headers for general inclusion.
 using namespace ldso_ba;
 
 namespace {

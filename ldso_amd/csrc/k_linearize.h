@@ -1,6 +1,8 @@
 // k_linearize.h -- the linearize kernel of the pass (Residuals.cc:15-217, the chunk's
 // AccumulatorApprox block) and the residual record it writes.
 #pragma once
+#include <hip/hip_ext.h>
+
 #include "ba_device.h"
 
 namespace {
@@ -37,7 +39,7 @@ struct LinParams {
     int fix;
     int accumulate;
     const float *ad_ht_delta;  // [pair_global][8] EnergyFunctional::adHTdeltaF (marginalisation pass)
-    const int *stop;           // ldso_ba_optimize: [win] first pass index a window skips - 1 (see opt_pass)
+    const int *stop;           // ldso_ba_optimize: [win] first pass index a window skips - 1 (see linearize_pass)
     int pass;                  // ldso_ba_optimize: this pass's index (0 = the initial linearizeAll)
     int aff_fix;               // bit 0: setting_affineOptModeA < 0, bit 1: ...B < 0 (JabF zeroed, Residuals.cc:186-187)
 };
@@ -867,6 +869,20 @@ __global__ __launch_bounds__(256, kLinBlocksPerCu) void k_linearize(LinParams P)
     if (!P.accumulate) return;
     wave_lds_sync();  // every lane has read its sums: the wave's LDS becomes the operand table
     top_mfma(lds_terms_w, lane, active, g, s, P.top_slab + (size_t)itemL * kTopVals);
+}
+
+template <bool kMarg>
+void launch_linearize(int img_mode, int nb, hipStream_t st, const LinParams &L, hipEvent_t ev_start = nullptr,
+                      hipEvent_t ev_stop = nullptr) {
+    if (ev_start) {  // timed: the dispatch itself stamps the events (no separate event packets in the stream)
+        if (img_mode == 3)
+            hipExtLaunchKernelGGL(k_linearize<3, kMarg>, dim3(nb), dim3(256), kLinLdsBytes, st, ev_start, ev_stop, 0, L);
+        else
+            hipExtLaunchKernelGGL(k_linearize<1, kMarg>, dim3(nb), dim3(256), kLinLdsBytes, st, ev_start, ev_stop, 0, L);
+        return;
+    }
+    if (img_mode == 3) k_linearize<3, kMarg><<<nb, 256, kLinLdsBytes, st>>>(L);
+    else k_linearize<1, kMarg><<<nb, 256, kLinLdsBytes, st>>>(L);
 }
 
 }  // namespace

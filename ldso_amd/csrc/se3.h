@@ -1,5 +1,5 @@
 // se3.h -- the double-precision SE(3) and FrameFramePrecalc arithmetic of the path, shared by the
-// host helpers (host_math.cpp) and the device GN loop (ldso_ba.hip k_step_resub), FP contraction
+// host helpers (host_math.cpp) and the device GN loop (k_step.h k_step_resub), FP contraction
 // off.  Pose restates Sophus's SE3 (thirdparty/Sophus/sophus/se3.hpp, so3.hpp) in its own
 // representation -- a unit quaternion (Eigen coeffs() order x, y, z, w) and a translation -- with
 // Sophus's operations statement for statement: SO3::expAndTheta (half-angle factors,
