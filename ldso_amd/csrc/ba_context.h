@@ -1,5 +1,5 @@
-// ba_context.h -- the host side's state: the timing slots, fail / HIP_TRY, the environment switches, the
-// owning buffers and events, the frame store and struct ldso_ba_ctx.
+// ba_context.h -- the host side's state: the timing slots, the environment switches, the allocation
+// generation of the captured graphs, the frame store and struct ldso_ba_ctx (on hip_owning.h's members).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -12,6 +12,7 @@
 #include "../../include/ldso_ba.h"
 #include "../../include/ldso_ct.h"
 #include "ba_device.h"
+#include "hip_owning.h"
 
 namespace {
 
@@ -20,14 +21,6 @@ enum : int { kSlotLinearize, kSlotPointSc, kSlotStitch,   kSlotResubstitute,
              kSlotFrameTh,   kSlotSolve,   kSlotActivate, kSlotStitchSum,    kNumKernels };
 const char *kKernelNames[kNumKernels] = {"k_linearize", "k_point_sc", "k_stitch",   "k_resubstitute",
                                          "k_frame_th",  "k_solve",    "k_activate", "k_stitch_sum"};
-
-inline int fail(int code, const std::string &msg) { return set_error(code, msg); }
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(-2, std::string(#expr) + ": " + hipGetErrorString(e_));  \
-    } while (0)
 
 // The environment switches ("environment"): debugging / A-B aids, read here and
 // nowhere else.  A flag is on when set and not "0".
@@ -51,109 +44,21 @@ Switches read_switches() {
 // ============================================================================================
 // host side
 // ============================================================================================
-// bumped by every device (re)allocation: a captured graph is valid while it is unchanged
+// Captured graphs hold device addresses, so launch_cached_graph replays a graph only while
+// g_alloc_gen is what it was at the capture.  Every device buffer of the BA unit is a GraphBuf, whose
+// alloc / release bump the counter (the contexts' buffers, the frame store, comm_exchange's scratch);
+// the tracker's plain DevBufs never appear in a BA graph and do not bump it.
 std::atomic<unsigned long long> g_alloc_gen{1};
+struct BumpAllocGen {
+    static void changed() { g_alloc_gen.fetch_add(1); }
+};
 template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() {  // a context's buffers go with it (ldso_ba_destroy)
-        if (p) release();
-    }
-    int alloc(size_t count) {
-        g_alloc_gen.fetch_add(1);
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        if (count == 0) return 0;
-        hipError_t e = hipMalloc(&p, count * sizeof(T));
-        if (e != hipSuccess) {
-            p = nullptr;
-            return fail(-3, std::string("hipMalloc failed: ") + hipGetErrorString(e));
-        }
-        n = count;  // only a successful allocation counts as capacity
-        return 0;
-    }
-    int ensure(size_t count) { return n >= count && p ? 0 : alloc(count); }  // keeps the pointer if it fits
-    void release() {
-        g_alloc_gen.fetch_add(1);
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    size_t bytes() const { return n * sizeof(T); }
-};
-
-// Grow-only pinned host staging of n elements (the address is kept while it fits), freed with the
-// context.  With hipHostMallocMapped in kFlags the device reads or writes it directly through dev.
-template <typename T, unsigned kFlags = hipHostMallocDefault>
-struct PinBuf {
-    T *p = nullptr, *dev = nullptr;
-    size_t n = 0;
-    PinBuf() = default;
-    PinBuf(const PinBuf &) = delete;
-    PinBuf &operator=(const PinBuf &) = delete;
-    ~PinBuf() {
-        if (p) (void)hipHostFree(p);
-    }
-    // the caller has made sure that nothing still uses the old buffer
-    int ensure(size_t count, size_t min_bytes = 64) {
-        if (p && n >= count) return 0;
-        if (p) (void)hipHostFree(p);
-        p = dev = nullptr;
-        n = 0;
-        const size_t bytes = std::max(count * sizeof(T), min_bytes);
-        HIP_TRY(hipHostMalloc((void **)&p, bytes, kFlags));
-        if (kFlags & hipHostMallocMapped) {
-            void *d = nullptr;
-            HIP_TRY(hipHostGetDevicePointer(&d, p, 0));
-            dev = static_cast<T *>(d);
-        }
-        n = bytes / sizeof(T);
-        return 0;
-    }
-};
-// coherent host memory the device addresses: its stores are visible to the host once the stream has
-// synchronised, and the host's stores to a launch that follows them
-using PinMapped = PinBuf<char, hipHostMallocCoherent | hipHostMallocMapped>;
-
-// an event created at first use and destroyed with its owner
-struct Event {
-    hipEvent_t e = nullptr;
-    Event() = default;
-    Event(const Event &) = delete;
-    Event &operator=(const Event &) = delete;
-    ~Event() {
-        if (e) (void)hipEventDestroy(e);
-    }
-    int ensure(unsigned flags) {
-        if (!e) HIP_TRY(hipEventCreateWithFlags(&e, flags));
-        return 0;
-    }
-};
-
-struct PendingEv {
-    int slot;
-    hipEvent_t a, b;
-};
-// the events of the timed launches, created ahead of them and reused (drain_events returns them)
-struct EventPool {
-    std::vector<hipEvent_t> free;
-    EventPool() = default;
-    EventPool(const EventPool &) = delete;
-    EventPool &operator=(const EventPool &) = delete;
-    ~EventPool() {
-        for (hipEvent_t e : free) (void)hipEventDestroy(e);
-    }
-};
+using GraphBuf = DevBuf<T, BumpAllocGen>;
 
 // Frame store (ldso_ba_frames_reserve ...): cap slots of one ImageLayout.  A slot's content is named
 // by the sequence number of the put that wrote it (seq, 0 = free).
 struct FrameStore {
-    DevBuf<float4> d_store;
+    GraphBuf<float4> d_store;
     ImageLayout lay;
     int cap = 0;
     std::vector<int64_t> id;
@@ -219,42 +124,42 @@ struct ldso_ba_ctx {
     int n_top_items = 0, n_sc_items = 0, n_pairs = 0, n_frames = 0, P_tot = 0, R_tot = 0;
     int max_frames = 0, kp_max = 0;  // the largest window of the load: its N and its WinDev::KP
     int dmax() const { return 8 * max_frames + 4; }  // ... and its WinDev::D
-    DevBuf<WinDev> d_wins;
+    GraphBuf<WinDev> d_wins;
     // the frames the kernels read: n_frames x img.frame_stride float4.  img is the layout of what is
     // loaded; img_mode_pref the one ldso_ba_load and ldso_ba_frames_reserve take
     // (LDSO_BA_TUNE_TILED_IMAGES, or ldso_ba_load's fallback to 1), which a load from the store, in
     // the store's layout, leaves alone.  img_tag[position of d_img] is the sequence number of the
     // store slot content copied there (0 = not from the store), so ldso_ba_load_frames copies only
     // positions whose tag differs.
-    DevBuf<float4> d_img;
+    GraphBuf<float4> d_img;
     ImageLayout img;
     int img_mode_pref = 3;
     std::vector<unsigned long long> img_tag;
     FrameStore store;
-    DevBuf<ldso_ct_immature> d_act_in;  // point activation staging (ldso_ba_activate_points)
-    DevBuf<ldso_ba_activation> d_act_out;
-    DevBuf<float> d_precalc, d_frame_th, d_pt_data, d_pt_out, d_pt_step;
-    DevBuf<double> d_adH, d_adT;
-    DevBuf<int> d_rs_slot, d_pt_nres, d_pair_win, d_frame_win, d_pt_host;
-    DevBuf<unsigned long long> d_pt_tgt;
-    DevBuf<uint8_t> d_rs_tgt, d_rs_flags;
-    DevBuf<int8_t> d_rs_state, d_rs_newstate;
-    DevBuf<float> d_rs_energy, d_rs_newenergy, d_rs_energy_wo;
-    DevBuf<float4> d_rs_center, d_rec_a;
-    DevBuf<float2> d_rec_b;
-    DevBuf<float> d_geo_snap;  // [pairs][kGeoSnap] (LinParams::geo_snap)
-    DevBuf<int4> d_top_items, d_sc_items;
-    DevBuf<int2> d_pair_items, d_host_items;
-    DevBuf<float> d_top_slab, d_sc_slab;
+    GraphBuf<ldso_ct_immature> d_act_in;  // point activation staging (ldso_ba_activate_points)
+    GraphBuf<ldso_ba_activation> d_act_out;
+    GraphBuf<float> d_precalc, d_frame_th, d_pt_data, d_pt_out, d_pt_step;
+    GraphBuf<double> d_adH, d_adT;
+    GraphBuf<int> d_rs_slot, d_pt_nres, d_pair_win, d_frame_win, d_pt_host;
+    GraphBuf<unsigned long long> d_pt_tgt;
+    GraphBuf<uint8_t> d_rs_tgt, d_rs_flags;
+    GraphBuf<int8_t> d_rs_state, d_rs_newstate;
+    GraphBuf<float> d_rs_energy, d_rs_newenergy, d_rs_energy_wo;
+    GraphBuf<float4> d_rs_center, d_rec_a;
+    GraphBuf<float2> d_rec_b;
+    GraphBuf<float> d_geo_snap;  // [pairs][kGeoSnap] (LinParams::geo_snap)
+    GraphBuf<int4> d_top_items, d_sc_items;
+    GraphBuf<int2> d_pair_items, d_host_items;
+    GraphBuf<float> d_top_slab, d_sc_slab;
     // d_sys = the exchange buffer: every window's packed system [sys_n], then the linearizeAll
     // energy / #IN pairs [n_win][2] (win_energy()), then doStepFromBackup's sumNID / numID
     // [n_win][2] (win_nid(), double: the ranks' float partials summed) -- contiguous, so that the
     // multi-GPU exchange reduces all three in ONE collective
-    DevBuf<double> d_item_energy, d_sys, d_stage;
+    GraphBuf<double> d_item_energy, d_sys, d_stage;
     size_t sys_n = 0;
     double *win_energy() const { return d_sys.p + sys_n; }
     double *win_nid() const { return d_sys.p + sys_n + 2 * (size_t)n_win; }
-    DevBuf<int2> d_sum_blocks;  // k_stitch_sum: {window, first packed element} per 256-thread block
+    GraphBuf<int2> d_sum_blocks;  // k_stitch_sum: {window, first packed element} per 256-thread block
     int n_sum_blocks = 0;
     // in-library multi-GPU exchange (ldso_ba_comm_init): RCCL communicator over this context's
     // device, the newest-frame energy slot stride (max over ranks, set at the first exchange
@@ -272,19 +177,19 @@ struct ldso_ba_ctx {
     }
     int64_t x_stride = 0;
     int64_t x_prun = 0;  // |idepth| run length per window slot (max local points over windows and ranks)
-    DevBuf<float> d_x_local, d_x_gathered;
+    GraphBuf<float> d_x_local, d_x_gathered;
     // device GN loop (ldso_ba_optimize): frame states, CalibHessian::value / value_zero and the
     // prior switches per window, the energy history
-    DevBuf<ldso_ba_frame_state> d_fstate;
-    DevBuf<double> d_calib_val, d_calib_zero, d_cprior, d_ehist;
-    DevBuf<int> d_stop, d_status;  // ldso_ba_optimize: per window, see FrameStepParams
-    DevBuf<int> d_add_priors;
-    DevBuf<float> d_xad;            // [win][kXadStride]
-    DevBuf<double> d_prior, d_x, d_ns;  // per-window (8N+4)-vectors: priors (HL diag, bL), x, nullspaces
-    DevBuf<double> d_ns_nm, d_ns_g;     // k_ortho_prep's Nm [7 vec] and per-window G | G^-1 | fast
+    GraphBuf<ldso_ba_frame_state> d_fstate;
+    GraphBuf<double> d_calib_val, d_calib_zero, d_cprior, d_ehist;
+    GraphBuf<int> d_stop, d_status;  // ldso_ba_optimize: per window, see FrameStepParams
+    GraphBuf<int> d_add_priors;
+    GraphBuf<float> d_xad;            // [win][kXadStride]
+    GraphBuf<double> d_prior, d_x, d_ns;  // per-window (8N+4)-vectors: priors (HL diag, bL), x, nullspaces
+    GraphBuf<double> d_ns_nm, d_ns_g;     // k_ortho_prep's Nm [7 vec] and per-window G | G^-1 | fast
     std::vector<double> ns_cache;       // the nullspaces k_ortho_prep last prepared (host copy) ...
     int ns_cache_null = -1;             // ... and their count; -1: nothing prepared
-    DevBuf<int> d_pt_win;
+    GraphBuf<int> d_pt_win;
     // marginalisation context (ldso_ba_load_marginalization): images borrowed from the parent
     // context's window, addPoint<2> sums, no prior shift in the SC pass
     bool marg = false;
@@ -292,22 +197,20 @@ struct ldso_ba_ctx {
     int n_cu = 256;  // compute units (k_stitch_host splits its blocks when the grid fits at once)  // k_stitch_host + k_stitch_host_sum (every window <= kHostStitchMaxN keyframes)
     const float4 *img_ext = nullptr;
     const float4 *images() const { return img_ext ? img_ext : d_img.p; }  // the frames the kernels read
-    DevBuf<float> d_adhtd;  // [pairs][8] adHTdeltaF
+    GraphBuf<float> d_adhtd;  // [pairs][8] adHTdeltaF
     int vec_total = 0;
     size_t sc_smem_max = 0;
-    bool timing = false;
-    unsigned timing_mask = ~0u;  // kernel slots bracketed by events when timing is on
+    unsigned timing_mask = ~0u;  // kernel slots bracketed by events when timing (timer.on) is on
     int top_chunk = 0;  // residuals per k_linearize wave (0 = automatic); LDSO_BA_TUNE_TOP_CHUNK
     int solve_exact = 0;  // LDSO_BA_TUNE_SOLVE_EXACT: 1 = the pivoted k_solve_reg / k_solve (bit-identical to the host)
     // image staging, allocated once and grown only: device float3 frame + mismatch flag, pinned host frame
-    DevBuf<float> d_img_stage;
-    DevBuf<int> d_img_flag;
+    GraphBuf<float> d_img_stage;
+    GraphBuf<int> d_img_flag;
     PinBuf<char> pin_img;
     int64_t xfer[4] = {0, 0, 0, 0};  // ldso_ba_transfer_stats
-    std::vector<PendingEv> pending;
-    EventPool ev_pool;
-    double kms[kNumKernels] = {0};
-    long long kcount[kNumKernels] = {0};
+    // timing-only events: no system-scope fence (its L2 write-back and invalidate would be timed, and
+    // would slow the kernel after the start event)
+    KernelTimer<kNumKernels> timer{hipEventDisableSystemFence, kKernelNames};
     std::vector<double> sys_host;  // last downloaded packed systems (per window, see sys_valid)
     std::vector<char> sys_valid;
     bool sys_host_valid = false;   // false => every window's host copy is stale
@@ -328,11 +231,11 @@ struct ldso_ba_ctx {
     bool th_host_valid = false;  // ... until the next pass, update or threshold exchange
     // ldso_ba_linearize_residuals: k_linearize runs on copies of the residual state so that the
     // context's own state (and its records, read by resubstitution) stay untouched
-    DevBuf<int8_t> d_sx_state, d_sx_newstate;
-    DevBuf<uint8_t> d_sx_flags;
-    DevBuf<float> d_sx_energy, d_sx_newenergy, d_sx_ewo;
-    DevBuf<float4> d_sx_center, d_sx_rec_a, d_pt_vals;
-    DevBuf<float2> d_sx_rec_b;
-    DevBuf<float> d_sx_geo_snap, d_jp_out;
-    DevBuf<double> d_sx_item;
+    GraphBuf<int8_t> d_sx_state, d_sx_newstate;
+    GraphBuf<uint8_t> d_sx_flags;
+    GraphBuf<float> d_sx_energy, d_sx_newenergy, d_sx_ewo;
+    GraphBuf<float4> d_sx_center, d_sx_rec_a, d_pt_vals;
+    GraphBuf<float2> d_sx_rec_b;
+    GraphBuf<float> d_sx_geo_snap, d_jp_out;
+    GraphBuf<double> d_sx_item;
 };

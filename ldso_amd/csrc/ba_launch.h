@@ -81,53 +81,11 @@ int InBatch::flush(ldso_ba_ctx *c) {
     return 0;
 }
 
-hipEvent_t get_event(ldso_ba_ctx *c) {
-    if (!c->ev_pool.free.empty()) {
-        hipEvent_t e = c->ev_pool.free.back();
-        c->ev_pool.free.pop_back();
-        return e;
-    }
-    hipEvent_t e;
-    // timing-only events: no system-scope fence (its L2 write-back and invalidate would be timed,
-    // and would slow the kernel after the start event)
-    (void)hipEventCreateWithFlags(&e, hipEventDisableSystemFence);
-    return e;
-}
-
-void drain_events(ldso_ba_ctx *c) {
-    for (auto &pe : c->pending) {
-        (void)hipEventSynchronize(pe.b);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, pe.a, pe.b);
-        c->kms[pe.slot] += ms;
-        c->kcount[pe.slot] += 1;
-        c->ev_pool.free.push_back(pe.a);
-        c->ev_pool.free.push_back(pe.b);
-    }
-    c->pending.clear();
-}
-
-// One launch into kernel-timing slot `slot`: when the slot is timed, two events from the pool are
-// handed to launch(a, b) and queued for drain_events; the launch's error becomes the call's.
-// record_on: the stream on which the events are recorded around the launch, or nullptr when the
-// launch stamps them itself.
+// One launch into kernel-timing slot `slot` (KernelTimer::launch), timed when timing is on and the
+// slot is in timing_mask.
 template <typename F>
 int timed_launch_events(ldso_ba_ctx *c, int slot, hipStream_t record_on, F &&launch) {
-    hipEvent_t a = nullptr, b = nullptr;
-    const bool timed = c->timing && ((c->timing_mask >> slot) & 1u);
-    if (timed) {
-        a = get_event(c);
-        b = get_event(c);
-        if (record_on) (void)hipEventRecord(a, record_on);
-    }
-    launch(a, b);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-2, std::string("launch ") + kKernelNames[slot] + ": " + hipGetErrorString(e));
-    if (timed) {
-        if (record_on) (void)hipEventRecord(b, record_on);
-        c->pending.push_back({slot, a, b});
-    }
-    return 0;
+    return c->timer.launch(slot, c->timer.on && ((c->timing_mask >> slot) & 1u), record_on, launch);
 }
 // timed_launch for a launch that takes the events itself (hipExtLaunchKernelGGL's start / stop
 // events, stamped by the dispatch): the stream carries no event packets around the kernel, which

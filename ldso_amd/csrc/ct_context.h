@@ -1,0 +1,71 @@
+// ct_context.h -- the tracker's host-side state: the timing slots and struct ldso_ct_ctx, whose members
+// (hip_owning.h) own every buffer and event: deleting the context frees them.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/ldso_ct.h"
+#include "hip_owning.h"
+#include "k_ct_pyramid.h"
+#include "k_ct_residual.h"
+#include "k_ct_immature.h"
+#include "k_ct_coarse_depth.h"
+
+namespace {
+
+constexpr int kMaxHyp = 256;
+// the timed launches' slots (ldso_ct_get_kernel_times / _kernel_name): each name below its slot
+enum : int { kCtSlotPyrDown,      kCtSlotPyrGrad, kCtSlotCalcRes, kCtSlotCalcGs,
+             kCtSlotMakeImmature, kCtSlotTrace,   kCtSlotIpCount, kNumCtKernels };
+const char *kCtKernelNames[kNumCtKernels] = {"k_ct_pyr_down",      "k_ct_pyr_grad", "k_ct_calc_res", "k_ct_calc_gs",
+                                             "k_ct_make_immature", "k_ct_trace",    "k_ct_ip_count"};
+
+}  // namespace
+
+struct ldso_ct_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    PyrParams pyr{};
+    int levels = 1;
+    float fx[LDSO_CT_MAX_LEVELS], fy[LDSO_CT_MAX_LEVELS], cx[LDSO_CT_MAX_LEVELS], cy[LDSO_CT_MAX_LEVELS];
+    float Ki[LDSO_CT_MAX_LEVELS][9];
+    bool have_k = false, have_frame = false, have_ref = false;
+    DevBuf<float> d_color, d_inten, d_B;
+    DevBuf<float4> d_dIp;
+    float new_exposure = 0, ref_exposure = 0, ref_a = 0, ref_b = 0;
+    // reference point clouds, all levels back to back
+    DevBuf<float4> d_pc;
+    int pc_off[LDSO_CT_MAX_LEVELS + 1] = {0};
+    // warped buffers of the last single-pose calcRes: n states and 2 n records, grown together
+    DevBuf<uint8_t> d_state;
+    DevBuf<float4> d_warp;
+    int last_lvl = -1, last_warped = 0;
+    // per-call staging.  The block partials live in coherent mapped host memory: the kernels write
+    // them straight to the host (a few KB), so a call needs no copy launch, only the synchronisation
+    PinBuf<CtPose> h_poses;
+    DevBuf<CtPose> d_poses;
+    PinMappedOf<double> parts;
+    // immature points (resident records, per-host tables, make staging, counters)
+    DevBuf<IpRec> d_ip;
+    int ip_n = 0, ip_max_host = -1;
+    DevBuf<float> d_hosts;
+    PinBuf<float> h_hosts;
+    DevBuf<float2> d_uv;
+    DevBuf<IpRec> d_mk;
+    DevBuf<int> d_counts;
+    PinBuf<int> h_counts;
+    // makeCoarseDepthL0 on the device (k_ct_coarse_depth.h): work buffers, allocated on first use;
+    // only the contributions grow
+    DevBuf<float4> d_cd_contrib;
+    PinBuf<float4> h_cd_contrib;  // pinned staging
+    DevBuf<float> d_cd_maps;      // idepth | weightSums, every level flat (2 x pyr.off[levels])
+    DevBuf<float4> d_cd_cand;     // a candidate per pixel of every level
+    DevBuf<int> d_cd_blk;         // [blocks] counts, then offsets; [blocks .. +levels] level offsets
+    PinMappedOf<int> cd_counts;   // pc_n per level
+    CdLevels cd_lv{};
+    int cd_interior = 0, cd_interior0 = 0;  // interior pixels of all levels / of level 0
+    Event cd_ev_a, cd_ev_b;
+    // kernel timing, on events with the default flags
+    KernelTimer<kNumCtKernels> timer{hipEventDefault, kCtKernelNames};
+};

@@ -1,7 +1,6 @@
 // k_ct_coarse_depth.h -- CoarseTracker::makeCoarseDepthL0 (CoarseTracker.cc:357-538) on the device:
 // the reference frame's point clouds pc_u / pc_v / pc_idepth / pc_color of every pyramid level from
-// the contributions (centerProjectedTo, HdiF) of the window's points.  Included by ldso_ct.hip
-// inside its unnamed namespace (PyrParams, kCtThreads, kWave).
+// the contributions (centerProjectedTo, HdiF) of the window's points.
 //
 //   k_ct_cd_gather   (from a BA context only) thread per residual of the window: the residual to
 //                    the reference frame with state IN writes its point's contribution
@@ -26,8 +25,14 @@
 // Arithmetic in the reference's statement order, contraction off, default (correctly rounded)
 // division and sqrtf.
 #pragma once
+#include <cstdint>
+
+#include "../../include/ldso_ba.h"
+#include "k_ct_pyramid.h"
 
 #pragma clang fp contract(off)
+
+namespace {
 
 // pixel of a contribution, or -1: int(c + 0.5f) truncates, so c + 0.5f in (-1, 0) is pixel 0; a
 // centre outside the image (the reference would write outside its arrays), a NaN or a hole is skipped
@@ -275,3 +280,5 @@ __global__ __launch_bounds__(kCtThreads) void k_ct_cd_write(const float4 *__rest
     const int pre = cd_block_prefix(emit, &total);
     if (emit) pc[(size_t)lvl_off[l] + blk_off_in_lvl[blockIdx.x] + pre] = v;
 }
+
+}  // namespace

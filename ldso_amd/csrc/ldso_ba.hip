@@ -46,8 +46,9 @@
 //   k_xad.h, k_activate.h, k_resubstitute.h, k_step.h, k_io.h
 //                     the 26 non-template kernels by stage, included below in the order the kernels have
 //                     always been defined in
-//   ba_context.h      the timing slots, the environment switches (read_switches), the owning buffers,
-//                     the frame store, struct ldso_ba_ctx
+//   hip_owning.h      shared with ldso_ct.hip: fail / HIP_TRY, the owning buffers and events, KernelTimer
+//   ba_context.h      the timing slots, the environment switches (read_switches), the allocation
+//                     generation, the frame store, struct ldso_ba_ctx
 //   ba_launch.h       staged uploads, timed launches, image staging, the parameter fillers and the
 //                     launches several entry points share
 //   ldso_ba.hip       the C ABI and the helpers between its extern "C" blocks (loads, the pass, the
@@ -278,7 +279,7 @@ void ldso_ba_destroy(ldso_ba_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    drain_events(c);  // the pending events go back to the pool, which destroys them
+    c->timer.drain();  // the pending events go back to the pool, which destroys them
     if (c->comm) (void)ncclCommDestroy(c->comm);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     // every member frees what it owns (device and pinned buffers, events, graph execs): the work
@@ -299,11 +300,11 @@ struct LoadList {
     int rc = 0;
     std::vector<InBatch::Item> ups;
     template <typename T>
-    void alloc(DevBuf<T> &buf, size_t count) {
+    void alloc(GraphBuf<T> &buf, size_t count) {
         if (!rc) rc = buf.alloc(std::max<size_t>(1, count));
     }
     template <typename T, typename V>
-    void put(DevBuf<T> &buf, const std::vector<V> &v) {
+    void put(GraphBuf<T> &buf, const std::vector<V> &v) {
         static_assert(sizeof(T) == sizeof(V), "uploaded as is");
         alloc(buf, v.size());
         if (!rc) ups.push_back({buf.p, v.data(), v.size() * sizeof(V)});
@@ -812,7 +813,7 @@ int comm_exchange(ldso_ba_ctx *c, bool accumulate, int pass, const Switches &sw)
             m[1] = std::max<int64_t>(m[1], D.P);
         }
         m[1] = (m[1] + 3) & ~(int64_t)3;  // the chain reads float4s of one rank's run
-        DevBuf<int64_t> t;
+        GraphBuf<int64_t> t;
         if (int rc = t.alloc(2)) return rc;
         HIP_TRY(hipMemcpyAsync(t.p, m, sizeof(m), hipMemcpyHostToDevice, st));
         NCCL_TRY(ncclAllReduce(t.p, t.p, 2, ncclInt64, ncclMax, c->comm, st));
@@ -1107,7 +1108,7 @@ int ldso_ba_sync(ldso_ba_ctx *c) {
     if (!c) return fail(-1, "null ctx");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    drain_events(c);
+    c->timer.drain();
     return 0;
 }
 
@@ -1526,7 +1527,7 @@ int ldso_ba_iterate(ldso_ba_ctx *c, int32_t iteration, double lambda, const doub
     };
     // direct launches by default: for this six-launch sequence hipGraphLaunch costs more host
     // time than it saves (one S7 window: 89 vs 95 us per call, tools/iter_probe.py)
-    if (!c->comm && !c->timing && sw.iterate_graph && !sw.no_graph) {
+    if (!c->comm && !c->timer.on && sw.iterate_graph && !sw.no_graph) {
         unsigned long long lb;
         std::memcpy(&lb, &lambda, sizeof(lb));
         // keyed by everything fixed at capture: lambda, n_null, the solve kernel, the stitch split,
@@ -1743,7 +1744,7 @@ int ldso_ba_optimize(ldso_ba_ctx *c, int32_t n_its, const ldso_ba_opt_settings *
             if ((r = gn_iteration(it))) return r;
         return 0;
     };
-    const bool use_graph = !c->comm && !c->timing && !sw.no_graph;
+    const bool use_graph = !c->comm && !c->timer.on && !sw.no_graph;
     if (use_graph && c->opt_warm) {
         std::vector<unsigned long long> key = capture_key(c, sw);  // the settings were installed above
         key.push_back((unsigned long long)(unsigned)n_its);
@@ -1951,18 +1952,9 @@ int ldso_ba_set_kernel_timing(ldso_ba_ctx *c, int32_t enable) {
     if (!c) return fail(-1, "null ctx");
     int rc = ldso_ba_sync(c);
     if (rc) return rc;
-    c->timing = enable != 0;
-    for (int i = 0; i < kNumKernels; i++) {
-        c->kms[i] = 0;
-        c->kcount[i] = 0;
-    }
-    // the events the timed launches will take, created now: hipEventCreate is a host call of tens of
-    // us, which inside a timed loop would stall the launches (kept in the pool across calls)
-    while (c->timing && c->ev_pool.free.size() < 256) {
-        hipEvent_t e;
-        if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) break;
-        c->ev_pool.free.push_back(e);
-    }
+    c->timer.on = enable != 0;
+    c->timer.reset();
+    if (c->timer.on) c->timer.reserve(256);  // the events the timed launches will take, created now
     return 0;
 }
 
@@ -1971,8 +1963,8 @@ int ldso_ba_get_kernel_times(ldso_ba_ctx *c, double *ms, int64_t *counts, int32_
     int rc = ldso_ba_sync(c);
     if (rc) return rc;
     for (int i = 0; i < n && i < kNumKernels; i++) {
-        if (ms) ms[i] = c->kms[i];
-        if (counts) counts[i] = c->kcount[i];
+        if (ms) ms[i] = c->timer.ms[i];
+        if (counts) counts[i] = c->timer.count[i];
     }
     return 0;
 }
