@@ -13,6 +13,9 @@
  *
  *   CoarseTracker::makeCoarseDepthL0    src/frontend/CoarseTracker.cc:357-538 -> ldso_ct_make_reference
  *                                                                              (+ _ba: from a BA pass)
+ *   PixelSelector::makeMaps             src/frontend/PixelSelector2.cc:27-316 -> ldso_ct_select_pixels
+ *   FullSystem::makeNewTraces           src/frontend/FullSystem.cc:1426-1482  -> ldso_ct_make_new_traces
+ *                                                                              (setting_pointSelection 0)
  *
  * The reference frame's point cloud (pc_u/pc_v/pc_idepth/pc_color per pyramid level) is built on
  * the device by ldso_ct_make_reference / ldso_ct_make_reference_ba, or handed over ready-made by
@@ -179,7 +182,65 @@ int ldso_ct_immature_download(ldso_ct_ctx *ctx, int32_t n, ldso_ct_immature *pts
 int ldso_ct_trace(ldso_ct_ctx *ctx, int32_t n_hosts, const float *krki, const float *kt, const float *aff,
                   int32_t *counts_out);
 
-/* kernel timing of the tracker's launches (same slots mechanism as ldso_ba) */
+/* ---- pixel selection: where the new keyframe's immature points go ---------------------------
+ *
+ *   PixelSelector::makeHists / select / makeMaps   src/frontend/PixelSelector2.cc:27-316 -> ldso_ct_select_pixels
+ *   FullSystem::makeNewTraces, pointSelection == 0  src/frontend/FullSystem.cc:1439-1461  -> ldso_ct_make_new_traces
+ *
+ * DSO's gradient-histogram selector on the context's new frame (levels 0-2 of the resident
+ * pyramid), bit for bit: selection, sub-selection, the records and their ordered compaction run
+ * on the device.  Not covered: setting_pointSelection == 1 (FeatureDetector::DetectCorners orders
+ * its candidates with an unstable std::sort, so ties have no order to reproduce, and its corners
+ * need ORB descriptors made on the host) and == 2 (OpenCV's RNG).  The coarse initializer's calls
+ * of makeMaps (th_factor 2, a density per level) are expressed by the parameters; nothing else of
+ * the initializer is here.
+ *
+ * select() looks its threshold up at thsSmoothed[(x >> 5) + (y >> 5) * (w / 32)], which leaves the
+ * grid makeHists fills when w or h is no multiple of 32: the strip right of the last whole block
+ * reads the first block of the next block row (reproduced); the strip below the last block row,
+ * and the right strip of that row, read entries the reference never writes (uninitialised memory
+ * there).  Those entries are 0 here, and the array holds every index select can form.
+ * Potentials above 32767 (the reference: undefined once the float leaves int's range) are 32767. */
+typedef struct ldso_ct_select_params {
+    float density;                          /* setting_desiredImmatureDensity / makeMaps' density */
+    int32_t recursions;                     /* makeMaps' recursionsLeft */
+    float th_factor;                        /* makeMaps' thFactor */
+    float min_grad_hist_cut;                /* setting_minGradHistCut */
+    float min_grad_hist_add;                /* setting_minGradHistAdd */
+    float grad_downweight_per_level;        /* setting_gradDownweightPerLevel */
+    int32_t select_direction_distribution;  /* setting_selectDirectionDistribution */
+} ldso_ct_select_params;
+/* Setting.cc:29, 83-87 and makeMaps' default arguments: 1500, 1, 1, 0.5, 7, 0.75, 1 */
+void ldso_ct_select_default_params(ldso_ct_select_params *p);
+
+/* PixelSelector::PixelSelector: random_pattern [width*height] is the selector's randomPattern (the
+ * caller's, because the reference fills it from libc rand()), potential its currentPotential (the
+ * constructor's 3; 1..32767).  The potential then persists from call to call as the member does;
+ * ldso_ct_select_potential reads it.  Refused on a context with fewer than 3 pyramid levels or
+ * with an image side of 16384 pixels or more. */
+int ldso_ct_select_init(ldso_ct_ctx *ctx, const uint8_t *random_pattern, int32_t potential);
+int ldso_ct_select_potential(ldso_ct_ctx *ctx, int32_t *out);
+
+#define LDSO_CT_SELECT_STATS 7
+/* makeMaps(newFrame, map_out, density, recursions, false, th_factor) on the context's new frame.
+ * map_out (may be NULL): [width*height] 0 / 1 / 2 / 4 as the reference's float map.
+ * stats_out (may be NULL): [LDSO_CT_SELECT_STATS] = makeMaps' return value, the last select's n2,
+ * n3, n4, the potential that pass used, the potential left for the next frame, select passes run.
+ * params NULL: the defaults.  Refused (< 0): no frame set, ldso_ct_select_init not called, density
+ * not finite or <= 0, recursions < 0. */
+int ldso_ct_select_pixels(ldso_ct_ctx *ctx, const ldso_ct_select_params *params, float *map_out, int32_t *stats_out);
+/* makeMaps, then makeNewTraces' walk over x in [3, w-4), y in [3, h-4): one ImmaturePoint per
+ * selected pixel at (x, y) with type = the map value and host = `host`, records whose energy_th is
+ * not finite dropped, the survivors in the walk's row-major order in out [capacity] (host memory;
+ * a copy, as with ldso_ct_make_immature: ldso_ct_immature_upload makes a set resident).
+ * *n_out = the records made.  capacity too small: < 0 with *n_out = the count needed, nothing
+ * written to out, and the potential put back to its value before the call, so that the retry
+ * repeats the selection.  stats_out as above. */
+int ldso_ct_make_new_traces(ldso_ct_ctx *ctx, const ldso_ct_select_params *params, int32_t host, int32_t capacity,
+                            ldso_ct_immature *out, int32_t *n_out, int32_t *stats_out);
+
+/* kernel timing of the tracker's launches (same slots mechanism as ldso_ba); the selection's
+ * launches take no slot */
 int ldso_ct_set_kernel_timing(ldso_ct_ctx *ctx, int32_t enable);
 int ldso_ct_get_kernel_times(ldso_ct_ctx *ctx, double *ms, int64_t *counts, int32_t n);
 const char *ldso_ct_kernel_name(int32_t i);

@@ -231,6 +231,17 @@ assert IMMATURE_DTYPE.itemsize == 128
 ACTIVATION_DTYPE = np.dtype([("idepth", "<f4"), ("status", "<i4"), ("in_mask", "<u4"), ("energy", "<f4")])
 IPS_NAMES = ("GOOD", "OOB", "OUTLIER", "SKIPPED", "BADCONDITION", "UNINITIALIZED")  # ImmaturePoint.h:31-38
 
+
+
+class LdsoCtSelectParams(C.Structure):
+    """ldso_ct_select_params (include/ldso_ct.h)"""
+    _fields_ = [("density", C.c_float), ("recursions", C.c_int32), ("th_factor", C.c_float),
+                ("min_grad_hist_cut", C.c_float), ("min_grad_hist_add", C.c_float),
+                ("grad_downweight_per_level", C.c_float), ("select_direction_distribution", C.c_int32)]
+
+
+SELECT_STATS = ("num", "n2", "n3", "n4", "potential_used", "potential_next", "passes")  # LDSO_CT_SELECT_STATS
+
 # (name, restype, argtypes) of every entry point declared in include/ldso_ct.h (coarse tracker)
 CT_ABI = [
     ("ldso_ct_create", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), i32p]),
@@ -255,6 +266,11 @@ CT_ABI = [
     ("ldso_ct_immature_upload", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     ("ldso_ct_immature_download", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     ("ldso_ct_trace", C.c_int, [C.c_void_p, C.c_int32, f32p, f32p, f32p, i32p]),
+    ("ldso_ct_select_default_params", None, [C.c_void_p]),
+    ("ldso_ct_select_init", C.c_int, [C.c_void_p, u8p, C.c_int32]),
+    ("ldso_ct_select_potential", C.c_int, [C.c_void_p, i32p]),
+    ("ldso_ct_select_pixels", C.c_int, [C.c_void_p, C.c_void_p, f32p, i32p]),
+    ("ldso_ct_make_new_traces", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, i32p, i32p]),
     ("ldso_ct_set_kernel_timing", C.c_int, [C.c_void_p, C.c_int32]),
     ("ldso_ct_get_kernel_times", C.c_int, [C.c_void_p, f64p, i64p, C.c_int32]),
     ("ldso_ct_kernel_name", C.c_char_p, [C.c_int32]),

@@ -11,6 +11,7 @@
 #include "k_ct_residual.h"
 #include "k_ct_immature.h"
 #include "k_ct_coarse_depth.h"
+#include "k_ct_select.h"
 
 namespace {
 
@@ -66,6 +67,17 @@ struct ldso_ct_ctx {
     CdLevels cd_lv{};
     int cd_interior = 0, cd_interior0 = 0;  // interior pixels of all levels / of level 0
     Event cd_ev_a, cd_ev_b;
+    // pixel selection (k_ct_select.h): the pattern and the potential from ldso_ct_select_init, the work
+    // buffers (sizes follow the image size) allocated by the first selection
+    DevBuf<uint8_t> d_sel_pattern, d_sel_map;
+    PinBuf<uint8_t> h_sel_map;
+    DevBuf<float> d_sel_ths_raw, d_sel_ths;  // ths [w32*h32]; thsSmoothed, every index select can form, the unwritten 0
+    DevBuf<unsigned> d_sel_mask;             // per cell, in traversal order
+    DevBuf<int> d_sel_n2, d_sel_nu;          // n2 at each cell's start; the direction-dependent cells
+    DevBuf<int> d_sel_blk;                   // block counts / offsets of the scans (two arrays)
+    DevBuf<int> d_sel_cnt;
+    PinBuf<int> h_sel_cnt;
+    int sel_potential = 0;  // currentPotential; 0: ldso_ct_select_init not called
     // kernel timing, on events with the default flags
     KernelTimer<kNumCtKernels> timer{hipEventDefault, kCtKernelNames};
 };

@@ -50,14 +50,11 @@ struct IpRec {  // ldso_ct_immature viewed as 32 words
 static_assert(sizeof(IpRec) == sizeof(ldso_ct_immature), "record layout");
 
 // new ImmaturePoint(newFrame, feat, type, HCalib): getInterpolatedElement33BiLin (GlobalFuncs.h:186-207)
-__global__ __launch_bounds__(kCtThreads) void k_ct_make_immature(const float4 *__restrict__ dI, int w, int h, int n,
-                                                                 const float2 *__restrict__ uv, float type, int host,
-                                                                 IpRec *__restrict__ out) {
-    const int k = blockIdx.x * kCtThreads + threadIdx.x;
-    if (k >= n) return;
+__device__ __forceinline__ IpRec ip_make_record(const float4 *__restrict__ dI, int w, int h, float u, float v,
+                                                float type, int host) {
     IpRec p;
-    p.u = uv[k].x;
-    p.v = uv[k].y;
+    p.u = u;
+    p.v = v;
     p.idepth_min = 0;
     p.idepth_max = __builtin_nanf("");
     p.quality = 10000;
@@ -99,7 +96,16 @@ __global__ __launch_bounds__(kCtThreads) void k_ct_make_immature(const float4 *_
     float e = 8 * kOutlierTH;
     e *= kOverallEnergyTHWeight * kOverallEnergyTHWeight;
     p.energy_th = ok ? e : __builtin_nanf("");
-    out[k] = p;
+    return p;
+}
+
+// thread per new point (ldso_ct_make_immature); k_ct_select.h's emit walk makes its records the same way
+__global__ __launch_bounds__(kCtThreads) void k_ct_make_immature(const float4 *__restrict__ dI, int w, int h, int n,
+                                                                 const float2 *__restrict__ uv, float type, int host,
+                                                                 IpRec *__restrict__ out) {
+    const int k = blockIdx.x * kCtThreads + threadIdx.x;
+    if (k >= n) return;
+    out[k] = ip_make_record(dI, w, h, uv[k].x, uv[k].y, type, host);
 }
 
 struct TraceParams {

@@ -17,6 +17,9 @@ Mirrors the reference class (src/frontend/CoarseTracker.cc) for the parts that r
                                           -> trace(krki, kt, aff)              FullSystem.cc:1157-1194,
                                              (records resident: immature_upload / immature_download)
                                                                                ImmaturePoint.cc:47-317
+    PixelSelector(w, h)                   -> select_init(pattern, potential)   PixelSelector2.cc:9-18
+    makeMaps(fh, map, density, ...)       -> select_pixels(density=..., ...)   PixelSelector2.cc:111-169
+    makeNewTraces (pointSelection == 0)   -> make_new_traces(host, ...)        FullSystem.cc:1439-1461
 
 No numerical work happens here; every call goes to libldso_ba.so (no fallback).
 """
@@ -209,3 +212,56 @@ class CoarseTracker:
         L.check(L.lib().ldso_ct_trace(self._h, int(krki.shape[0]), L.ptr(krki, L.f32p), L.ptr(kt, L.f32p),
                                       L.ptr(aff, L.f32p), L.ptr(c, L.i32p)))
         return c
+
+    # ---- pixel selection (PixelSelector::makeMaps, FullSystem::makeNewTraces with pointSelection 0) ----
+    @staticmethod
+    def _select_params(params: dict) -> "L.LdsoCtSelectParams":
+        p = L.LdsoCtSelectParams()
+        L.lib().ldso_ct_select_default_params(C.byref(p))
+        for k, v in params.items():
+            if k not in dict(p._fields_):
+                raise TypeError(f"unknown selection parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def select_init(self, pattern, potential: int = 3):
+        """The selector's randomPattern [width*height] (uint8) and its currentPotential."""
+        pattern = np.ascontiguousarray(pattern, np.uint8).reshape(-1)
+        assert pattern.size == self.width * self.height
+        L.check(L.lib().ldso_ct_select_init(self._h, L.ptr(pattern, L.u8p), int(potential)))
+
+    @property
+    def select_potential(self) -> int:
+        out = C.c_int32()
+        L.check(L.lib().ldso_ct_select_potential(self._h, C.byref(out)))
+        return int(out.value)
+
+    def select_pixels(self, **params):
+        """makeMaps on the new frame -> (map [height, width] of 0 / 1 / 2 / 4, stats dict over
+        _lib.SELECT_STATS).  params: the fields of ldso_ct_select_params (density, recursions, ...)."""
+        p = self._select_params(params)
+        m = np.zeros((self.height, self.width), np.float32)
+        st = np.zeros(len(L.SELECT_STATS), np.int32)
+        L.check(L.lib().ldso_ct_select_pixels(self._h, C.byref(p), L.ptr(m, L.f32p), L.ptr(st, L.i32p)))
+        return m, dict(zip(L.SELECT_STATS, st.tolist()))
+
+    def make_new_traces(self, host: int = 0, capacity: int | None = None, **params):
+        """makeMaps and makeNewTraces' walk on the device -> (records in row-major order, stats).
+        capacity None: room for twice the density, and the call repeated once with the count it
+        reports if that was too little."""
+        p = self._select_params(params)
+        st = np.zeros(len(L.SELECT_STATS), np.int32)
+        n = C.c_int32()
+        if capacity is not None:
+            cap = int(capacity)
+        else:  # (a density the library refuses still reaches it)
+            cap = min(int(2 * p.density) + 64, self.width * self.height) if 0 < p.density < np.inf else 64
+        for _ in range(2):
+            out = np.zeros(cap, L.IMMATURE_DTYPE)
+            rc = L.lib().ldso_ct_make_new_traces(self._h, C.byref(p), int(host), cap, out.ctypes.data, C.byref(n),
+                                                 L.ptr(st, L.i32p))
+            if rc == 0 or capacity is not None or n.value <= cap:
+                break
+            cap = int(n.value)  # the potential was put back: the retry repeats the selection
+        L.check(rc)
+        return out[:n.value].copy(), dict(zip(L.SELECT_STATS, st.tolist()))
