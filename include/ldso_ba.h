@@ -191,8 +191,10 @@ int ldso_ba_calc_l_energy(int32_t n_frames, const double *prior, const double *d
 /* ---- multi-GPU -------------------------------------------------------
  * Points are sharded by host frame: in host-frame order the window's points are cut into
  * `count` contiguous runs of equal residual counts (ldso_ba_load keeps run `rank`); a host is
- * split only where a cut falls inside it.  points_out (may be NULL) receives the caller indices
- * of run `rank`, *n_out their number. */
+ * split only where a cut falls inside it.  A window without residuals is cut into contiguous runs
+ * of equal point counts.  Host-frame order: host frames in window order, each host's points by
+ * point_rank (the caller's order without it).  A run may be empty.  points_out (may be NULL)
+ * receives the caller indices of run `rank`, *n_out their number. */
 int ldso_ba_shard_points(const ldso_ba_window *w, int32_t rank, int32_t count, int32_t *points_out,
                          int32_t *n_out);
 /* The packed layout the ranks reduce (ldso_ba_packed_system): upper triangles, row-major,
@@ -413,8 +415,11 @@ int ldso_ba_copy_packed(ldso_ba_ctx *ctx, void *dev_buf, int64_t n_doubles, int3
 /* Sharded setNewFrameEnergyTH (FullSystem.cc:2078-2109 over activeResiduals that target the
  * newest frame).  With points sharded, each rank holds part of the newest frame's
  * NewEnergyWithOutlier values; the exact nth_element needs all of them:
- *   newest_stride       max over this context's windows of its newest-frame residual count
- *                       (static after load; ranks agree on max-over-ranks as the slot size)
+ *   newest_stride       max over this context's windows of its newest-frame residual count, and
+ *                       at least 1 (static after load; ranks agree on max-over-ranks as the slot
+ *                       size).  A rank, or a whole window, without a residual into the newest frame
+ *                       exports pads only; a window whose gathered slots are all pads gets the
+ *                       reference's default threshold 12 * 12 * patternNum = 1152
  *   export_newest       writes [n_windows][stride] floats into a caller device buffer (-1 pads)
  *   frame_threshold_gathered  takes the all-gathered [n_ranks][n_windows][stride] buffer and
  *                       re-selects every window's newest-frame threshold on the device.

@@ -60,7 +60,9 @@ size_t sc_smem_bytes(int KP) {
 // SURVEY.md §8e's partition: points in host-frame order, cut into shard_count contiguous runs of
 // (as nearly as possible) equal residual counts, so a shard holds whole host frames except at
 // its two ends (a host is split only where a cut falls inside it, e.g. when shards outnumber
-// hosts).  Rank r owns the points whose first residual lies in [r T / G, (r + 1) T / G).
+// hosts).  Rank r owns the points whose first residual lies in [r T / G, (r + 1) T / G).  A window
+// without residuals (T = 0) is cut by point count instead: the point at position i of the order
+// goes to rank i G / P, so its runs are contiguous pieces of the host-frame order too.
 void shard_points(const ldso_ba_window &in, int rank, int count, std::vector<int> &out) {
     out.clear();
     // the device point order: host frames in window order, each host's points in features order
@@ -76,11 +78,12 @@ void shard_points(const ldso_ba_window &in, int rank, int count, std::vector<int
                              [&](int a, int c) { return in.point_rank[a] < in.point_rank[c]; });
     }
     const long long T = in.n_residuals;
-    long long acc = 0;
+    long long acc = 0, pos = 0;
     for (int p : order) {
-        const long long owner = T > 0 ? std::min<long long>(count - 1, acc * count / T) : p % count;
+        const long long owner = T > 0 ? std::min<long long>(count - 1, acc * count / T) : pos * count / in.n_points;
         if (owner == rank) out.push_back(p);
         acc += in.point_res_begin[p + 1] - in.point_res_begin[p];
+        pos++;
     }
 }
 

@@ -1882,7 +1882,7 @@ int ldso_ba_copy_packed(ldso_ba_ctx *c, void *buf, int64_t n, int32_t direction)
 
 int ldso_ba_newest_stride(ldso_ba_ctx *c, int64_t *stride) {
     if (!c || !stride) return fail(-1, "bad arguments");
-    int64_t m = 0;
+    int64_t m = 1;  // as comm_exchange: a slot of one pad where no residual targets a newest frame
     for (const WinDev &D : c->wd) m = std::max<int64_t>(m, D.newest_end - D.newest_begin);
     *stride = m;
     return 0;

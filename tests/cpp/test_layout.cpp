@@ -186,16 +186,18 @@ std::vector<int> host_order(const ldso_ba_window &in) {
     return o;
 }
 // SURVEY.md 8e's partition, restated: the owner of a point is the rank whose share [r T / G, (r + 1) T / G)
-// of the T residuals holds the point's first residual in device order; without residuals, p mod G
+// of the T residuals holds the point's first residual in device order; without residuals, the rank
+// whose share [r P / G, (r + 1) P / G) of the P positions of the device order holds the point's
 std::vector<int> ref_shard(const ldso_ba_window &in, int rank, int count) {
     std::vector<int> mine;
-    long long first = 0;
+    long long first = 0, pos = 0;
     for (int p : host_order(in)) {
         const long long T = in.n_residuals;
-        long long owner = T > 0 ? first * count / T : p % count;
+        long long owner = T > 0 ? first * count / T : pos * count / in.n_points;
         if (owner > count - 1) owner = count - 1;
         if (owner == rank) mine.push_back(p);
         first += in.point_res_begin[p + 1] - in.point_res_begin[p];
+        pos++;
     }
     return mine;
 }
