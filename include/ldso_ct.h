@@ -17,10 +17,14 @@
  *   FullSystem::makeNewTraces           src/frontend/FullSystem.cc:1426-1482  -> ldso_ct_make_new_traces
  *                                                                              (setting_pointSelection 0)
  *
+ *   CoarseTracker::trackNewestCoarse    src/frontend/CoarseTracker.cc:61-310  -> ldso_ct_track
+ *     one LM step of it on the host                                            (+ ldso_ct_lm_step)
+ *
  * The reference frame's point cloud (pc_u/pc_v/pc_idepth/pc_color per pyramid level) is built on
  * the device by ldso_ct_make_reference / ldso_ct_make_reference_ba, or handed over ready-made by
- * ldso_ct_set_reference; trackNewestCoarse's LM loop (CoarseTracker.cc:61-310) stays with the
- * caller and calls these entry points exactly where it calls calcRes / calcGSSSE.
+ * ldso_ct_set_reference.  trackNewestCoarse's LM loop (CoarseTracker.cc:61-310) runs on the device
+ * in one call, ldso_ct_track; a caller that keeps the loop calls ldso_ct_calc_res_gs and
+ * ldso_ct_lm_step exactly where the reference calls calcRes / calcGSSSE and solves its step.
  *
  * Conventions: poses are SE3 refToNew as a row-major 3x4 double matrix [R | t]
  * (Sophus::SE3::matrix3x4()); affine brightness parameters are AffLight (a, b) pairs;
@@ -128,6 +132,85 @@ int ldso_ct_calc_res_gs(ldso_ct_ctx *ctx, int32_t lvl, const double ref_to_new[1
  * of 4 exactly as buf_warped_* / buf_warped_n: out [n][8] = {idepth, u, v, dx, dy, residual,
  * weight, refColor}; *n_out = buf_warped_n.  out may be NULL to query n. */
 int ldso_ct_get_warped(ldso_ct_ctx *ctx, int32_t *n_out, float *out, int32_t capacity);
+
+/* ---- trackNewestCoarse (CoarseTracker.cc:61-310): the coarse-to-fine LM loop, visual-only -------
+ *
+ * With setting_vi_enable false InertialCoarseTrackerHessian::compute zeroes its energy, H_I, H_I_sc
+ * and b_I_sc and does nothing else (InertialCoarseTrackerHessian.cc:78-83); b_I, Hbb, Hab and bb keep
+ * the zeros of their initialisers (InertialCoarseTrackerHessian.h:58-68), and update / restore return
+ * at once.  What is left is the 8x8 system with bl = -b and resIOld = resINew = 0; the 15 zero rows
+ * that Hbb appends to Hl get a zero increment from Eigen's LDLT.  The inertial terms are not covered.
+ *
+ * The solve.  The reference adds H into the *upper* triangle of a zero Hl and calls Hl.ldlt(), which
+ * is LDLT<MatrixXd, Lower> and reads only the lower triangle: it factorises diag(Hl), so its step is
+ * inc_i = -b_i / (H_ii (1 + lambda)) (the 6x6 / 7x7 / stitched sub-systems of the affine modes
+ * likewise).  LDSO_CT_TRACK_SOLVE_REFERENCE is that step; LDSO_CT_TRACK_SOLVE_FULL, the default, is
+ * the symmetric system upstream DSO / LDSO solve (Mat88 Hl = H), with the pivoted LDLT of
+ * ldso_ba's solveSystemF.  lambda, the extrapolation factor, the cutoff repeat and AffLight's a, b
+ * are float as in the reference; the ABI carries them widened. */
+#define LDSO_CT_TRACK_SOLVE_FULL      0  /* the symmetric 8x8 system H(1+lambda on the diagonal), Eigen's pivoted LDLT */
+#define LDSO_CT_TRACK_SOLVE_REFERENCE 1  /* what the reference's expression evaluates to: the diagonal step */
+
+typedef struct ldso_ct_track_params {
+    float   coarse_cutoff_th;          /* setting_coarseCutoffTH, 20 */
+    double  lambda_increase;           /* setting_coarse_tracker_lambda_increase, 4.0 */
+    double  lambda_decrease;           /* setting_coarse_tracker_lambda_decrease, 0.5 */
+    float   affine_opt_mode_a, affine_opt_mode_b;   /* as ldso_ba_opt_settings */
+    int32_t max_iterations[5];         /* 10, 20, 50, 50, 50; each in [1, 1000] */
+    int32_t solve;                     /* LDSO_CT_TRACK_SOLVE_* */
+} ldso_ct_track_params;
+void ldso_ct_track_default_params(ldso_ct_track_params *p);
+
+typedef struct ldso_ct_track_result {
+    double  ref_to_new[12];            /* lastToNew_out (matrix3x4): the input pose after an abort (reason 1),
+                                          which returns before the reference assigns it */
+    double  aff[2];                    /* aff_g2l_out, with the final "< 0 -> 0" rule applied when ok; after an
+                                          abort the input rounded to float, as AffLight holds it */
+    double  last_residuals[5];         /* lastResiduals, NaN where a level was not reached */
+    double  flow[3];                   /* lastFlowIndicators (1000 if no level finished) */
+    int32_t ok;                        /* trackNewestCoarse's return value */
+    int32_t reason;                    /* 0 ok, 1 residual above 1.5 * min_res_for_abort at abort_level,
+                                          2 |a| / |b| too big, 3 relative affine too big */
+    int32_t abort_level;               /* -1 = no abort */
+    int32_t iterations[5];             /* LM iterations run per level, both visits of a repeated level summed */
+    int32_t repeated_level;            /* -1 = none */
+} ldso_ct_track_result;
+
+typedef struct ldso_ct_track_step {    /* one calcRes evaluation of the loop, in program order */
+    int32_t lvl, iteration;            /* iteration -1: the level's initial / cutoff-doubling evaluations */
+    int32_t accepted;                  /* iteration >= 0 only */
+    float   cutoff_th;                 /* the cutoff this evaluation used */
+    double  lambda;                    /* the lambda the step was solved with (0 for iteration -1) */
+    double  pose[12], aff[2];          /* what was evaluated */
+    double  rs[6];                     /* its Vec6 */
+    double  inc[8];                    /* the unscaled increment after extrapolation, iteration >= 0 only */
+} ldso_ct_track_step;
+
+/* n independent trackNewestCoarse runs on the context's new frame and reference cloud, one per start
+ * (ref_to_new_in [n][12], aff_in [n][2], min_res_for_abort [n][5]), concurrently: one launch, one
+ * workgroup per start, one synchronisation.  params NULL: the defaults.  trace (may be NULL): the
+ * evaluations of start 0, at most trace_capacity, *trace_n = how many there were (trace_n may be NULL).
+ * The sums of every evaluation are bitwise those ldso_ct_calc_res_gs returns at the same pose.
+ * Two deviations from the reference's statements, both so that this loop and a host loop over
+ * ldso_ct_calc_res_gs + ldso_ct_lm_step are one computation, bit for bit: an accepted pose is kept as
+ * the matrix that was evaluated and becomes a quaternion again (Eigen's Quaternion(Matrix3)) for the
+ * next step, where the reference keeps refToNew_new's quaternion; and SE3::exp's sine and cosine are
+ * the library's own (ct_lm.h, correctly rounded but for an error near 1e-4 ulp) on host and device,
+ * where the reference calls libm, whose last bit differs between glibc and the device library.
+ * Refused (< 0): what ldso_ct_calc_res refuses, coarsest_lvl outside [0, min(levels, 5)), n < 1,
+ * non-finite or non-positive params, an unknown solve, trace with trace_capacity < 1.
+ * Leaves the warped buffers invalid, as ldso_ct_set_reference does. */
+int ldso_ct_track(ldso_ct_ctx *ctx, int32_t n, const double *ref_to_new_in, const double *aff_in,
+                  int32_t coarsest_lvl, const double *min_res_for_abort, const ldso_ct_track_params *params,
+                  ldso_ct_track_result *out, ldso_ct_track_step *trace, int32_t trace_capacity, int32_t *trace_n);
+
+/* one LM step on the host with the statements the kernel runs (context-free): solve, extrapolation,
+ * scaling, the NaN guard, exp(inc) * pose, a/b update.  The pose enters through the matrix ABI
+ * (Eigen's Quaternion(Matrix3)); the kernel takes each accepted pose through the same door, so a
+ * host loop over ldso_ct_calc_res_gs and this call is ldso_ct_track's loop, evaluation for evaluation. */
+int ldso_ct_lm_step(const double H[64], const double b[8], double lambda, const double pose[12],
+                    const double aff[2], const ldso_ct_track_params *params,
+                    double inc_out[8], double pose_out[12], double aff_out[2]);
 
 /* ---- immature points: point creation and epipolar tracing ----------
  *

@@ -240,6 +240,23 @@ class LdsoCtSelectParams(C.Structure):
                 ("grad_downweight_per_level", C.c_float), ("select_direction_distribution", C.c_int32)]
 
 
+class LdsoCtTrackParams(C.Structure):
+    """ldso_ct_track_params (include/ldso_ct.h)"""
+    _fields_ = [("coarse_cutoff_th", C.c_float), ("lambda_increase", C.c_double), ("lambda_decrease", C.c_double),
+                ("affine_opt_mode_a", C.c_float), ("affine_opt_mode_b", C.c_float), ("max_iterations", C.c_int32 * 5),
+                ("solve", C.c_int32)]
+
+
+TRACK_SOLVE_FULL, TRACK_SOLVE_REFERENCE = 0, 1  # LDSO_CT_TRACK_SOLVE_*
+# ldso_ct_track_result / ldso_ct_track_step (include/ldso_ct.h)
+TRACK_RESULT_DTYPE = np.dtype([("ref_to_new", "<f8", (12,)), ("aff", "<f8", (2,)), ("last_residuals", "<f8", (5,)),
+                               ("flow", "<f8", (3,)), ("ok", "<i4"), ("reason", "<i4"), ("abort_level", "<i4"),
+                               ("iterations", "<i4", (5,)), ("repeated_level", "<i4")], align=True)
+TRACK_STEP_DTYPE = np.dtype([("lvl", "<i4"), ("iteration", "<i4"), ("accepted", "<i4"), ("cutoff_th", "<f4"),
+                             ("lambda", "<f8"), ("pose", "<f8", (12,)), ("aff", "<f8", (2,)), ("rs", "<f8", (6,)),
+                             ("inc", "<f8", (8,))], align=True)
+assert TRACK_RESULT_DTYPE.itemsize == 216 and TRACK_STEP_DTYPE.itemsize == 248 and C.sizeof(LdsoCtTrackParams) == 56
+
 SELECT_STATS = ("num", "n2", "n3", "n4", "potential_used", "potential_next", "passes")  # LDSO_CT_SELECT_STATS
 
 # (name, restype, argtypes) of every entry point declared in include/ldso_ct.h (coarse tracker)
@@ -262,6 +279,10 @@ CT_ABI = [
     ("ldso_ct_calc_res_gs", C.c_int,
      [C.c_void_p, C.c_int32, f64p, C.c_double, C.c_double, C.c_float, f64p, f64p, f64p]),
     ("ldso_ct_get_warped", C.c_int, [C.c_void_p, i32p, f32p, C.c_int32]),
+    ("ldso_ct_track_default_params", None, [C.c_void_p]),
+    ("ldso_ct_track", C.c_int, [C.c_void_p, C.c_int32, f64p, f64p, C.c_int32, f64p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_int32, i32p]),
+    ("ldso_ct_lm_step", C.c_int, [f64p, f64p, C.c_double, f64p, f64p, C.c_void_p, f64p, f64p, f64p]),
     ("ldso_ct_make_immature", C.c_int, [C.c_void_p, C.c_int32, f32p, C.c_float, C.c_int32, C.c_void_p]),
     ("ldso_ct_immature_upload", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     ("ldso_ct_immature_download", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),

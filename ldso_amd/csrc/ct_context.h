@@ -12,6 +12,7 @@
 #include "k_ct_immature.h"
 #include "k_ct_coarse_depth.h"
 #include "k_ct_select.h"
+#include "k_ct_track.h"
 
 namespace {
 
@@ -78,6 +79,11 @@ struct ldso_ct_ctx {
     DevBuf<int> d_sel_cnt;
     PinBuf<int> h_sel_cnt;
     int sel_potential = 0;  // currentPotential; 0: ldso_ct_select_init not called
+    // the LM loop (k_ct_track.h): starts in, results and start 0's trace out, all in mapped host memory
+    PinMappedOf<CtTrackStart> track_in;
+    PinMappedOf<ldso_ct_track_result> track_out;
+    PinMappedOf<ldso_ct_track_step> track_trace;
+    PinMappedOf<int> track_n;
     // kernel timing, on events with the default flags
     KernelTimer<kNumCtKernels> timer{hipEventDefault, kCtKernelNames};
 };

@@ -85,6 +85,9 @@ __device__ __forceinline__ void ct_gs_terms(float id, float u, float v, float dx
     }
 }
 
+// (k_ct_track.h's ct_track_point, ct_track_setup and ct_track_finish restate this kernel's <true> body, make_pose /
+// gs_affine and finish_calc_res / finish_calc_gs for the one-launch LM loop: change them together;
+// tests/test_track.py's lock-step holds the two to the same bits)
 template <bool kGS>
 __global__ __launch_bounds__(kCtThreads) void k_ct_calc_res(CtResParams P) {
     const CtPose &T = kGS ? P.pose0 : P.poses[blockIdx.y];

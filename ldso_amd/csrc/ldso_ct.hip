@@ -5,6 +5,7 @@
 //   k_ct_immature.h      k_ct_make_immature, k_ct_trace, k_ct_ip_count: immature points
 //   k_ct_coarse_depth.h  k_ct_cd_*: the reference cloud from the window's contributions
 //   k_ct_select.h        k_ct_sel_*: pixel selection (makeMaps) and makeNewTraces' walk
+//   k_ct_track.h         k_ct_track: trackNewestCoarse's LM loop, one launch (ct_lm.h: the loop's host/device half)
 //   ct_context.h         the timing slots and struct ldso_ct_ctx
 //   hip_owning.h         shared with ldso_ba.hip: fail / HIP_TRY, the owning buffers and events, KernelTimer
 #include <hip/hip_runtime.h>
@@ -23,6 +24,7 @@
 #include "k_ct_residual.h"
 #include "k_ct_immature.h"
 #include "k_ct_coarse_depth.h"
+#include "k_ct_track.h"
 #include "ct_context.h"
 
 #pragma clang fp contract(off)
@@ -450,6 +452,24 @@ int sel_make_maps(ldso_ct_ctx *c, const ldso_ct_select_params &p, int32_t stats[
     return 0;
 }
 
+// ---- the LM loop (k_ct_track.h, ct_lm.h) ---------------------------------------------------------
+// Setting.cc:82, 136-137, 65-66 (affineOptModeA / B), CoarseTracker.cc:73; the symmetric solve
+constexpr ldso_ct_track_params kTrackDefaults = {20.f, 4.0, 0.5, 1e12f, 1e8f, {10, 20, 50, 50, 50}, LDSO_CT_TRACK_SOLVE_FULL};
+
+int track_check_params(const ldso_ct_track_params &p) {
+    if (!std::isfinite(p.coarse_cutoff_th) || !(p.coarse_cutoff_th > 0)) return fail(-1, "coarse_cutoff_th must be finite and > 0");
+    if (!std::isfinite(p.lambda_increase) || !(p.lambda_increase > 0) || !std::isfinite(p.lambda_decrease) ||
+        !(p.lambda_decrease > 0))
+        return fail(-1, "lambda_increase and lambda_decrease must be finite and > 0");
+    if (!std::isfinite(p.affine_opt_mode_a) || !std::isfinite(p.affine_opt_mode_b))
+        return fail(-1, "affine_opt_mode_a / _b must be finite");
+    for (int l = 0; l < 5; l++)
+        if (p.max_iterations[l] < 1 || p.max_iterations[l] > ldso_ct::kTrackMaxIterations)
+            return fail(-1, "max_iterations out of range [1, 1000]");
+    if (p.solve != LDSO_CT_TRACK_SOLVE_FULL && p.solve != LDSO_CT_TRACK_SOLVE_REFERENCE) return fail(-1, "unknown solve mode");
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -840,6 +860,85 @@ int ldso_ct_calc_res_gs(ldso_ct_ctx *c, int32_t lvl, const double ref_to_new[12]
     finish_calc_res(c, lvl, 1, true, rs_out);
     c->last_lvl = lvl;
     finish_calc_gs(c, lvl, c->parts.p + res_parts, H_out, b_out);
+    return 0;
+}
+
+void ldso_ct_track_default_params(ldso_ct_track_params *p) {
+    if (p) *p = kTrackDefaults;
+}
+
+int ldso_ct_track(ldso_ct_ctx *c, int32_t n, const double *ref_to_new_in, const double *aff_in, int32_t coarsest_lvl,
+                  const double *min_res_for_abort, const ldso_ct_track_params *params, ldso_ct_track_result *out,
+                  ldso_ct_track_step *trace, int32_t trace_capacity, int32_t *trace_n) {
+    if (!c) return fail(-1, "null context");
+    if (coarsest_lvl < 0 || coarsest_lvl >= std::min(c->levels, 5))
+        return fail(-1, "coarsest_lvl out of range [0, min(levels, 5))");
+    int rc = check_level(c, coarsest_lvl);
+    if (rc) return rc;
+    if (n < 1) return fail(-1, "n must be >= 1");
+    if (!ref_to_new_in || !aff_in || !min_res_for_abort || !out) return fail(-1, "null argument");
+    const ldso_ct_track_params p = params ? *params : kTrackDefaults;
+    if ((rc = track_check_params(p))) return rc;
+    if (trace && trace_capacity < 1) return fail(-1, "trace_capacity must be >= 1 with a trace");
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = ct_grow(c, c->track_in, n)) || (rc = ct_grow(c, c->track_out, n)) || (rc = ct_grow(c, c->track_n, 1)) ||
+        (trace && (rc = ct_grow(c, c->track_trace, trace_capacity))))
+        return rc;
+    for (int k = 0; k < n; k++) {
+        CtTrackStart &S = c->track_in.p[k];
+        std::memcpy(S.ref_to_new, ref_to_new_in + 12 * (size_t)k, sizeof S.ref_to_new);
+        std::memcpy(S.aff, aff_in + 2 * (size_t)k, sizeof S.aff);
+        std::memcpy(S.min_res, min_res_for_abort + 5 * (size_t)k, sizeof S.min_res);
+    }
+    CtTrackParams P{};
+    for (int l = 0; l <= coarsest_lvl; l++) {
+        CtTrackLevel &L = P.lv[l];
+        L.pc = c->d_pc.p + c->pc_off[l];
+        L.img = c->d_dIp.p + c->pyr.off[l];
+        L.n = level_grid(c, l).n;
+        L.wl = c->pyr.wl[l];
+        L.hl = c->pyr.hl[l];
+        L.fxl = c->fx[l];
+        L.fyl = c->fy[l];
+        L.cxl = c->cx[l];
+        L.cyl = c->cy[l];
+        for (int k = 0; k < 9; k++) L.Ki[k] = c->Ki[l][k];
+    }
+    P.p = p;
+    P.starts = c->track_in.dev;
+    P.out = c->track_out.dev;
+    P.trace = trace ? c->track_trace.dev : nullptr;
+    P.trace_n = c->track_n.dev;
+    P.trace_capacity = trace ? trace_capacity : 0;
+    P.coarsest = coarsest_lvl;
+    P.ref_exposure = c->ref_exposure;
+    P.new_exposure = c->new_exposure;
+    P.ref_a = c->ref_a;
+    P.ref_b = c->ref_b;
+    c->last_lvl = -1;  // the warped buffers describe no evaluation of this call
+    k_ct_track<kTrackWaves><<<n, kTrackWaves * kWave, 0, c->stream>>>(P);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));  // results and trace are in host memory already
+    std::memcpy(out, c->track_out.p, (size_t)n * sizeof *out);
+    const int n_eval = c->track_n.p[0];
+    if (trace) std::memcpy(trace, c->track_trace.p, (size_t)std::min(n_eval, trace_capacity) * sizeof *trace);
+    if (trace_n) *trace_n = n_eval;
+    return 0;
+}
+
+int ldso_ct_lm_step(const double H[64], const double b[8], double lambda, const double pose[12], const double aff[2],
+                    const ldso_ct_track_params *params, double inc_out[8], double pose_out[12], double aff_out[2]) {
+    if (!H || !b || !pose || !aff || !inc_out || !pose_out || !aff_out) return fail(-1, "null argument");
+    const ldso_ct_track_params p = params ? *params : kTrackDefaults;
+    if (int rc = track_check_params(p)) return rc;
+    ldso_ct::LdltWork W;
+    ldso_ct::Pose cand;
+    const float a[2] = {(float)aff[0], (float)aff[1]};
+    float an[2];
+    ldso_ct::lm_step(H, b, (float)lambda, ldso_ct::pose_from_matrix(pose), a, p, W, inc_out, cand, an);
+    ldso_ct::pose_matrix(cand, pose_out);
+    aff_out[0] = an[0];
+    aff_out[1] = an[1];
     return 0;
 }
 

@@ -34,6 +34,10 @@ LDSO_HD inline void sin_cos(double x, double &s, double &c) {
 #endif
 }
 
+struct LibmSinCos {
+    LDSO_HD void operator()(double x, double &s, double &c) const { sin_cos(x, s, c); }
+};
+
 namespace ldso_ba {
 
 constexpr double kScaleXiTrans = 0.5, kScaleXiRot = 1.0, kScaleA = 10.0, kScaleB = 1000.0;
@@ -186,7 +190,10 @@ struct Pose {  // Sophus SE3: x -> R(q) x + t
     }
     // SE3::exp (se3.hpp:765-786) of the tangent [upsilon(3), omega(3)], with SO3::expAndTheta
     // (so3.hpp:577-605): the quaternion from the half-angle factors, not normalised
-    LDSO_HD static Pose exp(const double a[6]) {
+    // sc(x, s, c): the sine and cosine used (sin_cos: libm's; ct_lm.h passes one text for host and device)
+    LDSO_HD static Pose exp(const double a[6]) { return exp(a, LibmSinCos()); }
+    template <class SinCos>
+    LDSO_HD static Pose exp(const double a[6], SinCos sc) {
 #pragma clang fp contract(off)
         const double *w = a + 3;
         const double theta_sq = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
@@ -199,7 +206,7 @@ struct Pose {  // Sophus SE3: x -> R(q) x + t
             real = (1.0 - (1.0 / 8.0) * theta_sq) + (1.0 / 384.0) * theta_po4;
         } else {
             double sh, ch;
-            sin_cos(half_theta, sh, ch);
+            sc(half_theta, sh, ch);
             imag = sh / theta;
             real = ch;
         }
@@ -214,7 +221,7 @@ struct Pose {  // Sophus SE3: x -> R(q) x + t
             V = p.rotation_matrix();
         } else {
             double st, ct;
-            sin_cos(theta, st, ct);
+            sc(theta, st, ct);
             // se3.hpp:780 declares a new theta_sq = theta * theta here; fl(sqrt(x))^2 is often not
             // x, so expAndTheta's squaredNorm above is not reused
             const double theta_sq_v = theta * theta;

@@ -12,6 +12,9 @@ Mirrors the reference class (src/frontend/CoarseTracker.cc) for the parts that r
     calcRes(lvl, refToNew, aff, cutoff)   -> calc_res(lvl, T, aff, cutoff)     CoarseTracker.cc:540-673
     calcGSSSE(lvl, H, b, refToNew, aff)   -> calc_gs(lvl, T, aff)              CoarseTracker.cc:675-741
     calcRes + calcGSSSE at one pose       -> calc_res_gs(lvl, T, aff, cutoff)  CoarseTracker.cc:90-105, 218-245
+    trackNewestCoarse(fh, T, aff, lvl, minRes)
+                                          -> track(T, aff, min_res, ...)       CoarseTracker.cc:61-310
+                                             lm_step(H, b, lambda, T, aff)     CoarseTracker.cc:130-213
     new ImmaturePoint(newFrame, feat, ..) -> make_immature(uv, type, host)     ImmaturePoint.cc:14-39
     traceNewCoarse -> ImmaturePoint::traceOn
                                           -> trace(krki, kt, aff)              FullSystem.cc:1157-1194,
@@ -34,6 +37,30 @@ from . import _lib as L
 
 def _f32(a):
     return np.ascontiguousarray(a, np.float32)
+
+
+def track_params(**params) -> "L.LdsoCtTrackParams":
+    """ldso_ct_track_params: the defaults with the given fields replaced (max_iterations: 5 ints)."""
+    p = L.LdsoCtTrackParams()
+    L.lib().ldso_ct_track_default_params(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(p._fields_):
+            raise TypeError(f"unknown tracking parameter {k!r}")
+        setattr(p, k, (C.c_int32 * 5)(*v) if k == "max_iterations" else v)
+    return p
+
+
+def lm_step(H, b, lam: float, ref_to_new, aff_ab, **params):
+    """One LM step of trackNewestCoarse on the host (ldso_ct_lm_step) -> (inc [8], pose [3][4], aff [2])."""
+    H = np.ascontiguousarray(H, np.float64).reshape(64)
+    b = np.ascontiguousarray(b, np.float64).reshape(8)
+    T = np.ascontiguousarray(np.asarray(ref_to_new, np.float64)[:3, :4])
+    ab = np.ascontiguousarray(aff_ab, np.float64).reshape(2)
+    inc, To, abo = np.zeros(8), np.zeros((3, 4)), np.zeros(2)
+    p = track_params(**params)
+    L.check(L.lib().ldso_ct_lm_step(L.ptr(H, L.f64p), L.ptr(b, L.f64p), float(lam), L.ptr(T, L.f64p), L.ptr(ab, L.f64p),
+                                    C.byref(p), L.ptr(inc, L.f64p), L.ptr(To, L.f64p), L.ptr(abo, L.f64p)))
+    return inc, To, abo
 
 
 class CoarseTracker:
@@ -161,6 +188,35 @@ class CoarseTracker:
         T[...] = np.asarray(ref_to_new, np.float64)[:3, :4]
         L.check(fn(self._h, int(lvl), pT, float(aff_ab[0]), float(aff_ab[1]), float(cutoff_th), prs, pH, pb))
         return rs.copy(), H.copy(), b.copy()
+
+    def track(self, ref_to_new, aff_ab=(0.0, 0.0), min_res_for_abort=None, coarsest_lvl: int | None = None,
+              trace: int = 0, **params):
+        """trackNewestCoarse on the device, the whole LM loop in one call (ldso_ct_track).  One start
+        (ref_to_new [3][4], aff_ab [2]) or a batch ([n][3][4], [n][2]) run concurrently; min_res_for_abort
+        [5] or [n][5] (None: NaN, which never aborts, as FullSystem's first try).  coarsest_lvl None: the
+        coarsest level the reference tracks from, min(levels, 5) - 1.  params: the fields of
+        ldso_ct_track_params.  Returns the result records (_lib.TRACK_RESULT_DTYPE; one record for a single
+        start), and with trace > 0 also the first `trace` evaluations of start 0 (_lib.TRACK_STEP_DTYPE) and
+        how many there were."""
+        T = np.asarray(ref_to_new, np.float64)
+        single = T.ndim == 2
+        T = np.ascontiguousarray(T.reshape(-1, *T.shape[-2:])[:, :3, :4])
+        n = T.shape[0]
+        ab = np.ascontiguousarray(np.broadcast_to(np.asarray(aff_ab, np.float64).reshape(-1, 2), (n, 2)))
+        mr = np.full(5, np.nan) if min_res_for_abort is None else np.asarray(min_res_for_abort, np.float64)
+        mr = np.ascontiguousarray(np.broadcast_to(mr.reshape(-1, 5), (n, 5)))
+        lvl = min(self.levels, 5) - 1 if coarsest_lvl is None else int(coarsest_lvl)
+        p = track_params(**params)
+        out = np.zeros(n, L.TRACK_RESULT_DTYPE)
+        steps = np.zeros(max(int(trace), 0), L.TRACK_STEP_DTYPE)
+        n_steps = C.c_int32()
+        L.check(L.lib().ldso_ct_track(self._h, n, L.ptr(T, L.f64p), L.ptr(ab, L.f64p), lvl, L.ptr(mr, L.f64p),
+                                      C.byref(p), out.ctypes.data, steps.ctypes.data if steps.size else None,
+                                      int(steps.size), C.byref(n_steps)))
+        res = out[0] if single else out
+        if trace > 0:
+            return res, steps[:min(n_steps.value, steps.size)].copy(), int(n_steps.value)
+        return res
 
     def warped(self) -> np.ndarray:
         """buf_warped_* of the last calc_res as [n][8] {idepth, u, v, dx, dy, residual, weight, refColor}."""
