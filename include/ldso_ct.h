@@ -16,6 +16,8 @@
  *   PixelSelector::makeMaps             src/frontend/PixelSelector2.cc:27-316 -> ldso_ct_select_pixels
  *   FullSystem::makeNewTraces           src/frontend/FullSystem.cc:1426-1482  -> ldso_ct_make_new_traces
  *                                                                              (setting_pointSelection 0)
+ *   FeatureDetector::DetectCorners      src/frontend/FeatureDetector.cc:34-189 -> ldso_ct_detect_corners
+ *     and makeNewTraces' loop over it   src/frontend/FullSystem.cc:1428-1438   (setting_pointSelection 1)
  *
  *   CoarseTracker::trackNewestCoarse    src/frontend/CoarseTracker.cc:61-310  -> ldso_ct_track
  *     one LM step of it on the host                                            (+ ldso_ct_lm_step)
@@ -272,9 +274,8 @@ int ldso_ct_trace(ldso_ct_ctx *ctx, int32_t n_hosts, const float *krki, const fl
  *
  * DSO's gradient-histogram selector on the context's new frame (levels 0-2 of the resident
  * pyramid), bit for bit: selection, sub-selection, the records and their ordered compaction run
- * on the device.  Not covered: setting_pointSelection == 1 (FeatureDetector::DetectCorners orders
- * its candidates with an unstable std::sort, so ties have no order to reproduce, and its corners
- * need ORB descriptors made on the host) and == 2 (OpenCV's RNG).  The coarse initializer's calls
+ * on the device.  setting_pointSelection == 1, the reference's default, is ldso_ct_detect_corners
+ * below; == 2 (OpenCV's RNG) is not covered.  The coarse initializer's calls
  * of makeMaps (th_factor 2, a density per level) are expressed by the parameters; nothing else of
  * the initializer is here.
  *
@@ -322,8 +323,69 @@ int ldso_ct_select_pixels(ldso_ct_ctx *ctx, const ldso_ct_select_params *params,
 int ldso_ct_make_new_traces(ldso_ct_ctx *ctx, const ldso_ct_select_params *params, int32_t host, int32_t capacity,
                             ldso_ct_immature *out, int32_t *n_out, int32_t *stats_out);
 
-/* kernel timing of the tracker's launches (same slots mechanism as ldso_ba); the selection's
- * launches take no slot */
+/* ---- corner detection: the reference's default point selection (setting_pointSelection == 1) ----
+ *
+ *   FeatureDetector::DetectCorners       src/frontend/FeatureDetector.cc:34-130
+ *     ShiTomasiScore, IC_Angle           include/frontend/FeatureDetector.h:49-114
+ *   FeatureDetector::ComputeDescriptor   src/frontend/FeatureDetector.cc:132-189
+ *   FullSystem::makeNewTraces' loop      src/frontend/FullSystem.cc:1428-1438
+ *
+ * On level 0 of the context's new frame, in one call: the features in the reference's order (grid
+ * cells gx outer, gy inner, each cell's picks by descending score), one ImmaturePoint (type 1) per
+ * feature, and what loop closing later reads from the Feature: score, corner flag, angle, descriptor.
+ *
+ * Rules that are this library's, where the reference leaves the result open:
+ *  - Ties.  DetectCorners orders a cell's candidates with std::sort, which leaves equal scores in an
+ *    unspecified order.  Here the sort is stable: equal scores (-0 equals +0) keep candidate order
+ *    (x outer, y inner), which is one of the reference's possible outcomes (libstdc++'s insertion
+ *    sort for up to 16 elements is stable).  A score that is not finite (the square root of a
+ *    discriminant that rounding made negative) makes the reference's comparator undefined; here it
+ *    sorts after every number, in candidate order.
+ *  - float -> int (the descriptor's tap offsets and `int t = intensity`): a value that is not finite
+ *    or does not fit becomes INT_MIN, as x86's truncating conversion gives (undefined in C++).
+ *  - A corner whose orientation patch holds a non-finite intensity has a NaN angle; its taps then fall
+ *    outside the image in the reference (undefined); here a tap outside the 31 x 31 patch reads
+ *    INT_MIN, so that corner's descriptor is 32 zero bytes.
+ *  - The angle is (float)atan2((double)m_01, (double)m_10), where the reference calls atan2f, and the
+ *    descriptor's rotation is (float)cos / sin of the double angle by the library's own sine and cosine
+ *    (as ldso_ct_track's SE3::exp), where the reference calls cosf / sinf: libm's last bit differs
+ *    between glibc and the device library, a double result rounded once does not, but for rare cases.
+ *  - gridsize = int(sqrtf(w * h / n_features) + 0.5) outside [1, 30] is refused.  skip = 30 / gridsize
+ *    + 1 cells are left out at each border, so the cells start at (30 / gridsize + 1) * gridsize >= 31
+ *    and the last one ends at (w / gridsize - 30 / gridsize) * gridsize - 1 <= w - (30 / gridsize) *
+ *    gridsize - 1.  For gridsize <= 30 that product is at least 16 (gridsize 16), which leaves the 15
+ *    pixel orientation patch and the 13 pixel descriptor taps (|angle| <= pi, so the rotation is by
+ *    at most 0.055 rad: |offset| < 13.8) inside the image; for gridsize > 30 it is 0, the last cells
+ *    touch the border, and the reference's patch reads outside the image.
+ */
+typedef struct ldso_ct_feature {      /* Feature.h:86-90 */
+    float   score;                     /* Shi-Tomasi score */
+    float   angle;                     /* IC_Angle, 0 unless is_corner */
+    int32_t is_corner;
+    int32_t level;                     /* always 0 */
+    uint8_t descriptor[32];            /* zeros unless is_corner */
+} ldso_ct_feature;
+
+/* bit_pattern: the ORB sampling table bit_pattern_31_ [256 * 4] (the caller's, as randomPattern is for
+ * ldso_ct_select_init).  Refused: an entry outside [-13, 13], the table's range (see above). */
+int ldso_ct_corners_init(ldso_ct_ctx *ctx, const int32_t *bit_pattern /* [1024] */);
+
+#define LDSO_CT_CORNER_STATS 6
+/* DetectCorners(n_features, frame) and makeNewTraces' loop on the context's new frame: recs_out
+ * [capacity] the immature records (type 1, host = `host`; unlike ldso_ct_make_new_traces a record
+ * whose energy_th is not finite is kept: mode 1 has no such filter), feat_out [capacity] the features'
+ * score, corner flag, angle and descriptor, both in feature order (host memory).  *n_out = the features.
+ * stats_out (may be NULL): [LDSO_CT_CORNER_STATS] = gridsize, picks per cell k = floor(nfeatInGrid)
+ * + 1, candidates scored, features, corners, maxScore's bits.
+ * capacity too small: < 0 with *n_out = the count needed, nothing written to recs_out / feat_out.
+ * Refused (< 0): no frame set, ldso_ct_corners_init not called, n_features <= 0, gridsize < 1 or > 30.
+ * Does not touch the pixel selector's state. */
+int ldso_ct_detect_corners(ldso_ct_ctx *ctx, int32_t n_features, int32_t host, int32_t capacity,
+                           ldso_ct_immature *recs_out, ldso_ct_feature *feat_out, int32_t *n_out,
+                           int32_t *stats_out);
+
+/* kernel timing of the tracker's launches (same slots mechanism as ldso_ba); the selection's and the
+ * corner detection's launches take no slot */
 int ldso_ct_set_kernel_timing(ldso_ct_ctx *ctx, int32_t enable);
 int ldso_ct_get_kernel_times(ldso_ct_ctx *ctx, double *ms, int64_t *counts, int32_t n);
 const char *ldso_ct_kernel_name(int32_t i);

@@ -258,6 +258,11 @@ TRACK_STEP_DTYPE = np.dtype([("lvl", "<i4"), ("iteration", "<i4"), ("accepted", 
 assert TRACK_RESULT_DTYPE.itemsize == 216 and TRACK_STEP_DTYPE.itemsize == 248 and C.sizeof(LdsoCtTrackParams) == 56
 
 SELECT_STATS = ("num", "n2", "n3", "n4", "potential_used", "potential_next", "passes")  # LDSO_CT_SELECT_STATS
+# ldso_ct_feature (include/ldso_ct.h): what DetectCorners leaves on a Feature, 48 bytes
+FEATURE_DTYPE = np.dtype([("score", "<f4"), ("angle", "<f4"), ("is_corner", "<i4"), ("level", "<i4"),
+                          ("descriptor", "u1", (32,))])
+assert FEATURE_DTYPE.itemsize == 48
+CORNER_STATS = ("gridsize", "k", "candidates", "features", "corners", "max_score_bits")  # LDSO_CT_CORNER_STATS
 
 # (name, restype, argtypes) of every entry point declared in include/ldso_ct.h (coarse tracker)
 CT_ABI = [
@@ -292,6 +297,9 @@ CT_ABI = [
     ("ldso_ct_select_potential", C.c_int, [C.c_void_p, i32p]),
     ("ldso_ct_select_pixels", C.c_int, [C.c_void_p, C.c_void_p, f32p, i32p]),
     ("ldso_ct_make_new_traces", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, i32p, i32p]),
+    ("ldso_ct_corners_init", C.c_int, [C.c_void_p, i32p]),
+    ("ldso_ct_detect_corners", C.c_int,
+     [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, i32p, i32p]),
     ("ldso_ct_set_kernel_timing", C.c_int, [C.c_void_p, C.c_int32]),
     ("ldso_ct_get_kernel_times", C.c_int, [C.c_void_p, f64p, i64p, C.c_int32]),
     ("ldso_ct_kernel_name", C.c_char_p, [C.c_int32]),

@@ -12,6 +12,7 @@
 #include "k_ct_immature.h"
 #include "k_ct_coarse_depth.h"
 #include "k_ct_select.h"
+#include "k_ct_corners.h"
 #include "k_ct_track.h"
 
 namespace {
@@ -79,6 +80,16 @@ struct ldso_ct_ctx {
     DevBuf<int> d_sel_cnt;
     PinBuf<int> h_sel_cnt;
     int sel_potential = 0;  // currentPotential; 0: ldso_ct_select_init not called
+    // corner detection (k_ct_corners.h): the ORB table and umax from ldso_ct_corners_init; the work buffers,
+    // sized by the grid alone (every pixel of a cell a candidate), allocated by the first detection
+    DevBuf<int4> d_cor_pattern;
+    CorUmax cor_umax{};
+    bool cor_init = false;
+    DevBuf<int> d_cor_cell;               // [cells] pick counts, then [cells] their exclusive prefix
+    DevBuf<CorSlot> d_cor_slot, d_cor_feat;  // the picks per cell; the features in output order
+    DevBuf<int> d_cor_corner, d_cor_cnt;
+    DevBuf<ldso_ct_feature> d_cor_out;
+    PinMappedOf<int> cor_counts;          // the counters, written by the last launch
     // the LM loop (k_ct_track.h): starts in, results and start 0's trace out, all in mapped host memory
     PinMappedOf<CtTrackStart> track_in;
     PinMappedOf<ldso_ct_track_result> track_out;

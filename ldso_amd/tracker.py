@@ -23,6 +23,10 @@ Mirrors the reference class (src/frontend/CoarseTracker.cc) for the parts that r
     PixelSelector(w, h)                   -> select_init(pattern, potential)   PixelSelector2.cc:9-18
     makeMaps(fh, map, density, ...)       -> select_pixels(density=..., ...)   PixelSelector2.cc:111-169
     makeNewTraces (pointSelection == 0)   -> make_new_traces(host, ...)        FullSystem.cc:1439-1461
+    FeatureDetector()                     -> corners_init(bit_pattern)         FeatureDetector.cc:10-28
+    DetectCorners + makeNewTraces (pointSelection == 1)
+                                          -> detect_corners(n_features, host)  FeatureDetector.cc:34-189,
+                                                                               FullSystem.cc:1428-1438
 
 No numerical work happens here; every call goes to libldso_ba.so (no fallback).
 """
@@ -321,3 +325,29 @@ class CoarseTracker:
             cap = int(n.value)  # the potential was put back: the retry repeats the selection
         L.check(rc)
         return out[:n.value].copy(), dict(zip(L.SELECT_STATS, st.tolist()))
+
+    # ---- corner detection (FeatureDetector::DetectCorners, makeNewTraces with pointSelection 1) ----
+    def corners_init(self, bit_pattern):
+        """The ORB sampling table bit_pattern_31_ [256 * 4] (int32, entries in [-13, 13])."""
+        bit_pattern = np.ascontiguousarray(bit_pattern, np.int32).reshape(-1)
+        assert bit_pattern.size == 1024
+        L.check(L.lib().ldso_ct_corners_init(self._h, L.ptr(bit_pattern, L.i32p)))
+
+    def detect_corners(self, n_features: int, host: int = 0, capacity: int | None = None):
+        """DetectCorners(n_features) and makeNewTraces' loop on the new frame -> (immature records,
+        features (_lib.FEATURE_DTYPE), stats dict over _lib.CORNER_STATS), in feature order.
+        capacity None: room for twice n_features, and the call repeated once with the count it reports
+        if that was too little."""
+        st = np.zeros(len(L.CORNER_STATS), np.int32)
+        n = C.c_int32()
+        cap = int(capacity) if capacity is not None else max(2 * int(n_features), 0) + 64
+        for _ in range(2):
+            rec = np.zeros(cap, L.IMMATURE_DTYPE)
+            feat = np.zeros(cap, L.FEATURE_DTYPE)
+            rc = L.lib().ldso_ct_detect_corners(self._h, int(n_features), int(host), cap, rec.ctypes.data,
+                                                feat.ctypes.data, C.byref(n), L.ptr(st, L.i32p))
+            if rc == 0 or capacity is not None or n.value <= cap:
+                break
+            cap = int(n.value)
+        L.check(rc)
+        return rec[:n.value].copy(), feat[:n.value].copy(), dict(zip(L.CORNER_STATS, st.tolist()))
