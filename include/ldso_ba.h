@@ -359,6 +359,12 @@ typedef struct ldso_ba_activation {
 } ldso_ba_activation;
 int ldso_ba_activate_points(ldso_ba_ctx *ctx, int32_t win, int32_t n, const struct ldso_ct_immature *pts,
                             int32_t min_obs, ldso_ba_activation *out);
+/* The same for the records the tracker's last ldso_ct_select_activation selected (include/ldso_ct.h),
+ * read where they are: device to device, ordered with the tracker's stream by events.  out: host
+ * memory [n_selected], in the selection's walk order.  Refused (< 0): the tracker is on another device,
+ * it holds no selection, or the selection's n_hosts differs from the window's frame count. */
+int ldso_ba_activate_points_tracker(ldso_ba_ctx *ctx, int32_t win, const struct ldso_ct_ctx *tracker, int32_t min_obs,
+                                    ldso_ba_activation *out);
 
 /* One hot-path pass over all loaded windows, asynchronous on the context stream:
  *   linearizeAll(fix) + applyRes(true) + setNewFrameEnergyTH, and if accumulate != 0

@@ -384,6 +384,76 @@ int ldso_ct_detect_corners(ldso_ct_ctx *ctx, int32_t n_features, int32_t host, i
                            ldso_ct_immature *recs_out, ldso_ct_feature *feat_out, int32_t *n_out,
                            int32_t *stats_out);
 
+/* ---- activation candidates: which immature points become points ------------------------------
+ *
+ *   CoarseDistanceMap::makeDistanceMap / growDistBFS / addIntoDistFinal   src/frontend/CoarseTracker.cc:795-932
+ *   FullSystem::activatePointsMT, the walk                                src/frontend/FullSystem.cc:1220-1298
+ *
+ * On level 1 (w1 = width >> 1, h1 = height >> 1, whatever the context's pyramid holds): the map of
+ * growth steps to the nearest projected active point, then the walk over the resident immature
+ * records that deletes, keeps or selects each for optimizeImmaturePoint, every accepted candidate
+ * stamped into the map before the next one is looked at.  The result equals the sequential walk for
+ * every input; the records never leave the device: ldso_ct_trace leaves them
+ * resident, ldso_ba_activate_points_tracker (include/ldso_ba.h) reads the selection.
+ * The policy part (FullSystem.cc:1199-1218: currentMinActDist from ef->nPoints) stays with the caller.
+ *
+ * Rules that are this library's:
+ *  - float -> int (`int u = ptp[0] / ptp[2] + 0.5f`): a value that is not finite or does not fit
+ *    becomes INT_MIN, as x86's truncating conversion gives (undefined in C++); it fails `u > 0`.
+ *  - Frames whose level 1 has a side of 32768 pixels or more are refused. */
+
+/* makeDistanceMap from n active points in host arrays: uvd [n][3] = PointHessian u, v, idepth_scaled,
+ * host [n] the index of each point's host frame into krki1 [n_hosts][9] (K[1] R Ki[0], row-major) and
+ * kt1 [n_hosts][3] (K[1] t), host -> newest frame in float as activatePointsMT builds them; the caller
+ * leaves the newest frame's points out.  n_hosts in [1, 16].  The map and the tables stay in the context
+ * for ldso_ct_select_activation.  map_out (may be NULL): [w1*h1] the map after makeDistanceMap, 1000
+ * where no growth arrived. */
+int ldso_ct_make_distance_map(ldso_ct_ctx *ctx, int32_t n_hosts, const float *krki1, const float *kt1, int32_t n,
+                              const float *uvd, const int32_t *host, float *map_out);
+/* The same with the seeds read on the device from window `win` of a bundle-adjustment context: every
+ * point's u, v and current idepth (SCALE_IDEPTH is 1) of every host frame but `newest` (-1: the
+ * window's last frame); n_hosts is the window's frame count.  Ordered with the BA context's stream by
+ * events, not by the host.  Refused (< 0): another device, a marginalisation context, a context that
+ * holds a shard of its points, a window whose image size differs from the tracker's. */
+int ldso_ct_make_distance_map_ba(ldso_ct_ctx *ctx, const struct ldso_ba_ctx *ba, int32_t win, int32_t newest,
+                                 const float *krki1, const float *kt1, float *map_out);
+
+typedef struct ldso_ct_actsel_params {
+    float current_min_act_dist;  /* currentMinActDist after the caller's update, in [0, 4] */
+    float min_trace_quality;     /* setting_minTraceQuality */
+    int32_t newest_host;         /* the host the walk skips; -1: none; -2: n_hosts - 1 */
+} ldso_ct_actsel_params;
+/* FullSystem.h's initial currentMinActDist, Setting.cc's setting_minTraceQuality, the last host */
+#define LDSO_CT_ACTSEL_PARAMS_INIT {2.0f, 3.0f, -2}
+
+#define LDSO_CT_ACT_KEEP 0
+#define LDSO_CT_ACT_DELETE 1
+#define LDSO_CT_ACT_OPTIMIZE 2
+/* The walk of activatePointsMT over the n resident records, with the map and the tables of the last
+ * distance-map call (refused without one).  Walk order: host ascending, and within a host the resident
+ * order: the caller keeps each host's records in the host frame's feature order, as the reference
+ * walks them.  flagged (may be NULL: none): [n_hosts] flaggedForMarginalization.  params NULL: the
+ * defaults above.
+ * disposition_out (may be NULL): [n] LDSO_CT_ACT_* per resident record; a record of newest_host is
+ * KEEP and untouched.  selected_idx_out (may be NULL): room for n indices; the first *n_selected_out
+ * are the OPTIMIZE records' resident indices in walk order.  Those records are copied, in that order,
+ * to the context's selection, which ldso_ba_activate_points_tracker reads.  counts_out (may be NULL):
+ * [4] = records kept, deleted, selected, and the kept ones that could activate but were too close.
+ * compact != 0: the resident set becomes the KEEP records in their previous order (every OPTIMIZE
+ * point leaves the immature set whatever its optimisation returns, FullSystem.cc:1313-1336), so
+ * ldso_ct_immature_download then takes kept records; compact == 0 leaves the resident set untouched.
+ * Refused (< 0): no distance map, current_min_act_dist outside [0, 4], newest_host out of range, a
+ * resident record whose host is >= the map's n_hosts. */
+int ldso_ct_select_activation(ldso_ct_ctx *ctx, const ldso_ct_actsel_params *params, const uint8_t *flagged,
+                              int32_t compact, int32_t *disposition_out, int32_t *selected_idx_out,
+                              int32_t *n_selected_out, int32_t *counts_out);
+/* the last selection's n = *n_selected_out records, in walk order (a copy: tests and callers that
+ * optimise on the host) */
+int ldso_ct_selection_download(ldso_ct_ctx *ctx, int32_t n, ldso_ct_immature *pts);
+/* n more records behind the resident set (the new keyframe's, after makeNewTraces): only they cross
+ * the bus; the resident ones move on the device if the buffer has to grow. */
+int ldso_ct_immature_append(ldso_ct_ctx *ctx, int32_t n, const ldso_ct_immature *pts);
+
 /* kernel timing of the tracker's launches (same slots mechanism as ldso_ba); the selection's and the
  * corner detection's launches take no slot */
 int ldso_ct_set_kernel_timing(ldso_ct_ctx *ctx, int32_t enable);

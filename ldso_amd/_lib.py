@@ -206,6 +206,7 @@ ABI = [
     ("ldso_ba_load_marginalization", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(LdsoBaWindow)]),
     ("ldso_ba_marginalize_points", C.c_int, [C.c_void_p, f32p, f64p, f64p]),
     ("ldso_ba_activate_points", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("ldso_ba_activate_points_tracker", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     # device-resident frame store
     ("ldso_ba_frames_reserve", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     ("ldso_ba_frame_put", C.c_int, [C.c_void_p, C.c_int64, f32p]),
@@ -247,6 +248,13 @@ class LdsoCtTrackParams(C.Structure):
                 ("solve", C.c_int32)]
 
 
+class LdsoCtActselParams(C.Structure):
+    """ldso_ct_actsel_params (include/ldso_ct.h); the defaults are LDSO_CT_ACTSEL_PARAMS_INIT"""
+    _fields_ = [("current_min_act_dist", C.c_float), ("min_trace_quality", C.c_float), ("newest_host", C.c_int32)]
+
+
+ACT_KEEP, ACT_DELETE, ACT_OPTIMIZE = 0, 1, 2  # LDSO_CT_ACT_*
+ACTSEL_COUNTS = ("kept", "deleted", "selected", "rejected_by_distance")
 TRACK_SOLVE_FULL, TRACK_SOLVE_REFERENCE = 0, 1  # LDSO_CT_TRACK_SOLVE_*
 # ldso_ct_track_result / ldso_ct_track_step (include/ldso_ct.h)
 TRACK_RESULT_DTYPE = np.dtype([("ref_to_new", "<f8", (12,)), ("aff", "<f8", (2,)), ("last_residuals", "<f8", (5,)),
@@ -292,6 +300,11 @@ CT_ABI = [
     ("ldso_ct_immature_upload", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     ("ldso_ct_immature_download", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     ("ldso_ct_trace", C.c_int, [C.c_void_p, C.c_int32, f32p, f32p, f32p, i32p]),
+    ("ldso_ct_make_distance_map", C.c_int, [C.c_void_p, C.c_int32, f32p, f32p, C.c_int32, f32p, i32p, f32p]),
+    ("ldso_ct_make_distance_map_ba", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, f32p, f32p, f32p]),
+    ("ldso_ct_select_activation", C.c_int, [C.c_void_p, C.c_void_p, u8p, C.c_int32, i32p, i32p, i32p, i32p]),
+    ("ldso_ct_selection_download", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    ("ldso_ct_immature_append", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     ("ldso_ct_select_default_params", None, [C.c_void_p]),
     ("ldso_ct_select_init", C.c_int, [C.c_void_p, u8p, C.c_int32]),
     ("ldso_ct_select_potential", C.c_int, [C.c_void_p, i32p]),

@@ -224,6 +224,13 @@ class BAContext:
                                                   out.ctypes.data))
         return out
 
+    def activate_points_tracker(self, win: int, tracker, min_obs: int = 1) -> np.ndarray:
+        """The same for the records a CoarseTracker's last select_activation selected, read on the
+        device (ldso_ba_activate_points_tracker) -> ldso_ba_activation records in the selection's order."""
+        out = np.zeros(getattr(tracker, "_as_sel_n", 0), L.ACTIVATION_DTYPE)
+        L.check(self._lib.ldso_ba_activate_points_tracker(self._h, int(win), tracker._h, int(min_obs), out.ctypes.data))
+        return out
+
     def update_points(self, win: int, vals: np.ndarray):
         """ldso_ba_update_points: [P][4] (idepth_scaled, idepth_zero_scaled, priorF, deltaF), caller order."""
         v = np.ascontiguousarray(vals, np.float32).reshape(-1, 4)

@@ -138,6 +138,7 @@ struct ldso_ba_ctx {
     FrameStore store;
     GraphBuf<ldso_ct_immature> d_act_in;  // point activation staging (ldso_ba_activate_points)
     GraphBuf<ldso_ba_activation> d_act_out;
+    Event act_ev_a, act_ev_b;  // ldso_ba_activate_points_tracker: tracker -> k_activate, k_activate -> tracker
     GraphBuf<float> d_precalc, d_frame_th, d_pt_data, d_pt_out, d_pt_step;
     GraphBuf<double> d_adH, d_adT;
     GraphBuf<int> d_rs_slot, d_pt_nres, d_pair_win, d_frame_win, d_pt_host;

@@ -14,6 +14,7 @@
 #include "k_ct_select.h"
 #include "k_ct_corners.h"
 #include "k_ct_track.h"
+#include "k_ct_actsel.h"
 
 namespace {
 
@@ -95,6 +96,31 @@ struct ldso_ct_ctx {
     PinMappedOf<ldso_ct_track_result> track_out;
     PinMappedOf<ldso_ct_track_step> track_trace;
     PinMappedOf<int> track_n;
+    // activation candidates (k_ct_actsel.h): the level-1 map and the host tables of the last distance-map
+    // call; the work buffers, sized by the frame (map, bins) and by the resident set's capacity, allocated
+    // by the first call that needs them; the OPTIMIZE records of the last selection
+    DevBuf<int> d_as_map;
+    PinBuf<int> h_as_map;
+    DevBuf<float> d_as_hosts, d_as_uvd;  // [n_hosts][KRKi 9, Kt 3] of level 1; the host seeds
+    PinBuf<float> h_as_hosts;
+    DevBuf<int> d_as_seed_host;
+    DevBuf<uint8_t> d_as_flag;
+    PinBuf<uint8_t> h_as_flag;
+    int as_n_hosts = 0;
+    bool as_have_map = false;
+    DevBuf<AsCand> d_as_cand;
+    DevBuf<AsEntry> d_as_entry;
+    DevBuf<int> d_as_disp, d_as_out;  // the walk's states; dispositions [n], then selected indices [n]
+    PinBuf<int> h_as_out;
+    DevBuf<int> d_as_blk, d_as_tot, d_as_cnt;  // d_as_cnt: the counters, then the bins and the scatter's cursors
+    PinBuf<int> h_as_cnt;
+    PinMappedOf<int> as_counts;       // the counters, written by the last launch
+    // d_ip_alt: the compaction's target, then swapped with d_ip (so the immature set is held twice once a
+    // call has compacted); after ldso_ct_immature_append has grown d_ip it is the old, smaller buffer, which
+    // stays allocated until the next compaction replaces it with one of d_ip's capacity
+    DevBuf<IpRec> d_as_selected, d_ip_alt;
+    int as_sel_n = -1, as_sel_hosts = 0;    // -1: no selection yet
+    Event as_ev_a, as_ev_b;
     // kernel timing, on events with the default flags
     KernelTimer<kNumCtKernels> timer{hipEventDefault, kCtKernelNames};
 };

@@ -104,6 +104,8 @@ int ldso_ba::ba_ref_view(const ldso_ba_ctx *c, int win, ldso_ba::BaRefView *out)
     out->tgt = c->d_rs_tgt.p + D.res_base;
     out->slot = c->d_rs_slot.p + D.res_base;
     out->pt_out = c->d_pt_out.p + (size_t)D.point_base * 12;
+    out->pt_data = c->d_pt_data.p + (size_t)D.point_base * LDSO_BA_POINT_STRIDE;
+    out->pt_host = c->d_pt_host.p + D.point_base;
     out->R = D.R;
     out->P = D.P;
     out->N = D.N;
@@ -1078,6 +1080,48 @@ int ldso_ba_activate_points(ldso_ba_ctx *c, int32_t win, int32_t n, const ldso_c
     A.min_obs = min_obs;
     int rc = timed_launch(c, kSlotActivate, c->stream, [&] { k_activate<<<(n + 3) / 4, 256, 0, c->stream>>>(A); });
     if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->d_act_out.p, (size_t)n * sizeof(ldso_ba_activation), hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int ldso_ba_activate_points_tracker(ldso_ba_ctx *c, int32_t win, const ldso_ct_ctx *tracker, int32_t min_obs,
+                                    ldso_ba_activation *out) {
+    if (!c || win < 0 || win >= c->n_win || !tracker) return fail(-1, "bad arguments");
+    CtSelectionView V;
+    int rc = ct_selection_view(tracker, &V);
+    if (rc) return rc;
+    if (V.device != c->device) return fail(-1, "the tracker is on a different device");
+    if (V.n < 0) return fail(-1, "the tracker holds no selection: call ldso_ct_select_activation first");
+    if (V.n_hosts != c->wh[win].N) return fail(-1, "the selection's n_hosts differs from the window's frame count");
+    const int n = V.n;
+    if (n == 0) return 0;
+    if (!out) return fail(-1, "bad arguments");
+    HIP_TRY(hipSetDevice(c->device));
+    if ((size_t)n > c->d_act_out.n || !c->d_act_out.p)
+        if ((rc = c->d_act_out.alloc(n))) return rc;
+    if ((rc = c->act_ev_a.ensure(hipEventDisableTiming)) || (rc = c->act_ev_b.ensure(hipEventDisableTiming))) return rc;
+    // read the records behind what the tracker's stream holds now; its later work waits for the read
+    hipStream_t ts = static_cast<hipStream_t>(V.stream);
+    HIP_TRY(hipEventRecord(c->act_ev_a.e, ts));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->act_ev_a.e, 0));
+    ActParams A;
+    A.wins = c->d_wins.p;
+    A.img = c->images();
+    A.precalc = c->d_precalc.p;
+    A.pts = static_cast<const ldso_ct_immature *>(V.records);
+    A.out = c->d_act_out.p;
+    A.frame_stride = c->img.frame_stride;
+    A.tpr = c->img.tiles_per_row;
+    A.img_mode = c->img.mode;
+    A.win = win;
+    A.n = n;
+    A.min_obs = min_obs;
+    rc = timed_launch(c, kSlotActivate, c->stream, [&] { k_activate<<<(n + 3) / 4, 256, 0, c->stream>>>(A); });
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(c->act_ev_b.e, c->stream));
+    HIP_TRY(hipStreamWaitEvent(ts, c->act_ev_b.e, 0));
     HIP_TRY(hipMemcpyAsync(out, c->d_act_out.p, (size_t)n * sizeof(ldso_ba_activation), hipMemcpyDeviceToHost,
                            c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

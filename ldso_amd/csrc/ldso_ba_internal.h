@@ -120,6 +120,8 @@ struct BaRefView {
     const uint8_t *tgt;      // [R] target frame
     const int *slot;         // [R] record slot
     const float *pt_out;     // [P][12], [0] = HdiF
+    const float *pt_data;    // [P][LDSO_BA_POINT_STRIDE]: u, v, idepth_scaled, ...
+    const int *pt_host;      // [P] host frame
     int R, P, N, rec_base;
     int width, height, device;
     void *stream;            // hipStream_t every BA kernel runs on
@@ -128,6 +130,17 @@ struct BaRefView {
     bool have_pass;          // a linearisation pass has run since the last load
 };
 int ba_ref_view(const ldso_ba_ctx *ba, int win, BaRefView *out);
+
+// The tracker's last activation selection as ldso_ba_activate_points_tracker reads it: the OPTIMIZE
+// records (ldso_ct_immature) in walk order, resident on the tracker's device.
+struct CtSelectionView {
+    const void *records;
+    int n;        // -1: no selection yet
+    int n_hosts;  // of the distance-map call the selection used
+    int device;
+    void *stream;
+};
+int ct_selection_view(const ldso_ct_ctx *ct, CtSelectionView *out);
 
 int frame_precalc(int N, const ldso_ba_frame_state *fr, const float calib[4], float *out);
 int set_adjoints(int N, const ldso_ba_frame_state *fr, double *adH, double *adT, double *cPrior);

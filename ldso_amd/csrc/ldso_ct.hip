@@ -5,6 +5,7 @@
 //   k_ct_immature.h      k_ct_make_immature, k_ct_trace, k_ct_ip_count: immature points
 //   k_ct_coarse_depth.h  k_ct_cd_*: the reference cloud from the window's contributions
 //   k_ct_select.h        k_ct_sel_*: pixel selection (makeMaps) and makeNewTraces' walk
+//   k_ct_actsel.h        k_ct_as_*: the distance map and activatePointsMT's walk
 //   k_ct_track.h         k_ct_track: trackNewestCoarse's LM loop, one launch (ct_lm.h: the loop's host/device half)
 //   ct_context.h         the timing slots and struct ldso_ct_ctx
 //   hip_owning.h         shared with ldso_ba.hip: fail / HIP_TRY, the owning buffers and events, KernelTimer
@@ -25,6 +26,7 @@
 #include "k_ct_immature.h"
 #include "k_ct_coarse_depth.h"
 #include "k_ct_track.h"
+#include "k_ct_actsel.h"
 #include "ct_context.h"
 
 #pragma clang fp contract(off)
@@ -54,6 +56,17 @@ int ldso_ba::ct_frame_view(const ldso_ct_ctx *c, ldso_ba::CtFrameView *out) {
     out->device = c->device;
     out->stream = (void *)c->stream;
     out->have_frame = c->have_frame;
+    return 0;
+}
+
+// the BA context's view of the last activation selection (ldso_ba_activate_points_tracker)
+int ldso_ba::ct_selection_view(const ldso_ct_ctx *c, ldso_ba::CtSelectionView *out) {
+    if (!c || !out) return fail(-1, "null argument");
+    out->records = c->d_as_selected.p;
+    out->n = c->as_sel_n;
+    out->n_hosts = c->as_sel_hosts;
+    out->device = c->device;
+    out->stream = (void *)c->stream;
     return 0;
 }
 
@@ -471,6 +484,61 @@ int cor_grid(const ldso_ct_ctx *c, int n_features, CorGrid &G) {
     G.ncy = std::max(0, gridY - 2 * G.skip);
     G.k = (int)std::floor(nfeatInGrid) + 1;
     G.kk = std::min(G.k, gridsize * gridsize);
+    return 0;
+}
+
+// ---- activation candidates (k_ct_actsel.h) --------------------------------------------------------
+constexpr ldso_ct_actsel_params kActselDefaults = LDSO_CT_ACTSEL_PARAMS_INIT;
+
+AsGrid as_grid(const ldso_ct_ctx *c) {
+    AsGrid G;
+    G.w1 = c->pyr.w >> 1;  // wG[1], hG[1], whatever the context's pyramid holds
+    G.h1 = c->pyr.h >> 1;
+    G.bw = (G.w1 + (1 << kAsBinShift) - 1) >> kAsBinShift;
+    G.bh = (G.h1 + (1 << kAsBinShift) - 1) >> kAsBinShift;
+    return G;
+}
+
+// the checks both distance-map calls share, and the level-1 host tables onto the device
+int as_begin_map(ldso_ct_ctx *c, int n_hosts, const float *krki1, const float *kt1) {
+    if (n_hosts < 1 || n_hosts > kAsMaxHosts) return fail(-1, "n_hosts out of range [1, 16]");
+    if (!krki1 || !kt1) return fail(-1, "null host tables");
+    const AsGrid G = as_grid(c);
+    if (G.w1 >= kAsMaxSide || G.h1 >= kAsMaxSide)
+        return fail(-1, "level 1 of the frame is " + std::to_string(G.w1) + " x " + std::to_string(G.h1) +
+                            ": the activation selection packs a pixel into 2 x 15 bits (sides below 32768)");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t npx = (size_t)G.w1 * G.h1, n_tab = (size_t)kAsMaxHosts * 12;
+    int rc;
+    if ((rc = c->d_as_map.ensure(npx)) || (rc = c->h_as_map.ensure(npx)) || (rc = c->d_as_hosts.ensure(n_tab)) ||
+        (rc = c->h_as_hosts.ensure(n_tab)))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the staging buffer may still feed a previous copy
+    c->as_have_map = false;
+    for (int i = 0; i < n_hosts; i++) {
+        std::memcpy(c->h_as_hosts.p + 12 * (size_t)i, krki1 + 9 * (size_t)i, 9 * sizeof(float));
+        std::memcpy(c->h_as_hosts.p + 12 * (size_t)i + 9, kt1 + 3 * (size_t)i, 3 * sizeof(float));
+    }
+    HIP_TRY(hipMemcpyAsync(c->d_as_hosts.p, c->h_as_hosts.p, (size_t)n_hosts * 12 * sizeof(float), hipMemcpyHostToDevice,
+                           c->stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)c->d_as_map.p, kAsFar, npx, c->stream));
+    return 0;
+}
+
+// growDistBFS over the seeded map, the map to the caller if asked
+int as_finish_map(ldso_ct_ctx *c, int n_hosts, float *map_out) {
+    const AsGrid G = as_grid(c);
+    const size_t npx = (size_t)G.w1 * G.h1;
+    k_ct_as_grow<<<dim3((G.w1 + kAsTile - 1) / kAsTile, (G.h1 + kAsTile - 1) / kAsTile), kAsGrowThreads, 0, c->stream>>>(
+        c->d_as_map.p, G);
+    HIP_TRY(hipGetLastError());
+    if (map_out) {
+        HIP_TRY(hipMemcpyAsync(c->h_as_map.p, c->d_as_map.p, npx * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < npx; i++) map_out[i] = (float)c->h_as_map.p[i];
+    }
+    c->as_n_hosts = n_hosts;
+    c->as_have_map = true;
     return 0;
 }
 
@@ -1163,6 +1231,186 @@ int ldso_ct_trace(ldso_ct_ctx *c, int32_t n_hosts, const float *krki, const floa
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (counts_out) std::memcpy(counts_out, c->h_counts.p, 6 * sizeof(int));
+    return 0;
+}
+
+int ldso_ct_make_distance_map(ldso_ct_ctx *c, int32_t n_hosts, const float *krki1, const float *kt1, int32_t n,
+                              const float *uvd, const int32_t *host, float *map_out) {
+    if (!c) return fail(-1, "null context");
+    if (n < 0 || (n > 0 && (!uvd || !host))) return fail(-1, "bad seed arguments");
+    for (int k = 0; k < n; k++)
+        if (host[k] < 0 || host[k] >= n_hosts) return fail(-1, "a seed's host index is outside [0, n_hosts)");
+    int rc = as_begin_map(c, n_hosts, krki1, kt1);
+    if (rc) return rc;
+    if (n > 0) {
+        // (the stream is idle but for the copies above: as_begin_map synchronised)
+        if ((rc = c->d_as_uvd.ensure(3 * (size_t)n)) || (rc = c->d_as_seed_host.ensure(n))) return rc;
+        HIP_TRY(hipMemcpyAsync(c->d_as_uvd.p, uvd, 3 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->d_as_seed_host.p, host, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        k_ct_as_seed<<<(n + kCtThreads - 1) / kCtThreads, kCtThreads, 0, c->stream>>>(
+            c->d_as_uvd.p, 3, c->d_as_seed_host.p, n, n_hosts, -1, c->d_as_hosts.p, as_grid(c), c->d_as_map.p);
+        HIP_TRY(hipGetLastError());
+    }
+    if ((rc = as_finish_map(c, n_hosts, map_out))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the caller's arrays may be reused on return
+    return 0;
+}
+
+int ldso_ct_make_distance_map_ba(ldso_ct_ctx *c, const ldso_ba_ctx *ba, int32_t win, int32_t newest, const float *krki1,
+                                 const float *kt1, float *map_out) {
+    if (!c) return fail(-1, "null context");
+    if (!ba) return fail(-1, "null bundle-adjustment context");
+    ldso_ba::BaRefView V;
+    int rc = ldso_ba::ba_ref_view(ba, win, &V);
+    if (rc) return rc;
+    if (V.device != c->device) return fail(-1, "the bundle-adjustment context is on a different device");
+    if (V.marg) return fail(-1, "a marginalisation context holds no active window");
+    if (V.sharded) return fail(-1, "the context holds a shard of its points: the distance map needs the whole window");
+    if (V.width != c->pyr.w || V.height != c->pyr.h)
+        return fail(-1, "the tracker's frame size differs from the window's images");
+    if (newest < -1 || newest >= V.N) return fail(-1, "newest out of range");
+    if (newest < 0) newest = V.N - 1;
+    if ((rc = as_begin_map(c, V.N, krki1, kt1))) return rc;
+    if ((rc = c->as_ev_a.ensure(hipEventDisableTiming)) || (rc = c->as_ev_b.ensure(hipEventDisableTiming))) return rc;
+    if (V.P > 0) {
+        // read the points behind what the BA stream holds now; its later work waits for the read
+        hipStream_t bs = static_cast<hipStream_t>(V.stream);
+        HIP_TRY(hipEventRecord(c->as_ev_a.e, bs));
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->as_ev_a.e, 0));
+        k_ct_as_seed<<<(V.P + kCtThreads - 1) / kCtThreads, kCtThreads, 0, c->stream>>>(
+            V.pt_data, LDSO_BA_POINT_STRIDE, V.pt_host, V.P, V.N, newest, c->d_as_hosts.p, as_grid(c), c->d_as_map.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->as_ev_b.e, c->stream));
+        HIP_TRY(hipStreamWaitEvent(bs, c->as_ev_b.e, 0));
+    }
+    return as_finish_map(c, V.N, map_out);
+}
+
+int ldso_ct_select_activation(ldso_ct_ctx *c, const ldso_ct_actsel_params *params, const uint8_t *flagged,
+                              int32_t compact, int32_t *disposition_out, int32_t *selected_idx_out,
+                              int32_t *n_selected_out, int32_t *counts_out) {
+    if (!c) return fail(-1, "null context");
+    if (!c->as_have_map) return fail(-1, "no distance map: call ldso_ct_make_distance_map first");
+    const int n_hosts = c->as_n_hosts, n = c->ip_n;
+    ldso_ct_actsel_params p = params ? *params : kActselDefaults;
+    if (!params || p.newest_host == -2) p.newest_host = n_hosts - 1;
+    if (!(p.current_min_act_dist >= 0 && p.current_min_act_dist <= 4))
+        return fail(-1, "current_min_act_dist outside [0, 4]");
+    if (std::isnan(p.min_trace_quality)) return fail(-1, "min_trace_quality is NaN");
+    if (p.newest_host < -1 || p.newest_host >= n_hosts) return fail(-1, "newest_host out of range");
+    if (n_hosts <= c->ip_max_host) return fail(-1, "an immature point's host index is >= the distance map's n_hosts");
+    HIP_TRY(hipSetDevice(c->device));
+    const AsGrid G = as_grid(c);
+    const int n_bins = G.bw * G.bh, nb = sel_blocks(n);
+    const size_t cap = std::max<size_t>(c->d_ip.n, 1);
+    int rc;
+    if ((rc = c->d_as_cand.ensure(cap)) || (rc = c->d_as_entry.ensure(cap)) || (rc = c->d_as_disp.ensure(cap)) ||
+        (rc = c->d_as_out.ensure(2 * cap)) || (rc = c->h_as_out.ensure(2 * cap)) ||
+        (rc = c->d_as_blk.ensure((size_t)(kAsMaxHosts + 1) * sel_blocks((int)cap))) ||
+        (rc = c->d_as_tot.ensure(kAsMaxHosts + 1)) || (rc = c->d_as_cnt.ensure(kAsCnts + 2 * (size_t)n_bins + 1)) ||
+        (rc = c->h_as_cnt.ensure(kAsCnts)) || (rc = c->as_counts.ensure(kAsCnts)) ||
+        (rc = c->d_as_selected.ensure(cap)) || (rc = c->d_as_flag.ensure(kAsMaxHosts)) ||
+        (rc = c->h_as_flag.ensure(kAsMaxHosts)) || (compact && (rc = c->d_ip_alt.ensure(cap))))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the staging buffers and the selection may still be read
+    c->as_sel_n = -1;
+    int32_t counts[4] = {0, 0, 0, 0};
+    int max_host = -1;
+    if (n > 0) {
+        for (int i = 0; i < kAsMaxHosts; i++) c->h_as_flag.p[i] = (flagged && i < n_hosts && flagged[i]) ? 1 : 0;
+        HIP_TRY(hipMemcpyAsync(c->d_as_flag.p, c->h_as_flag.p, kAsMaxHosts, hipMemcpyHostToDevice, c->stream));
+        // the counters, the bins' counts (then offsets) and the scatter's cursors: one buffer, one memset
+        int *cnt = c->d_as_cnt.p, *bin = cnt + kAsCnts, *cursor = bin + n_bins + 1;
+        HIP_TRY(hipMemsetAsync(cnt, 0, (kAsCnts + 2 * (size_t)n_bins + 1) * sizeof(int), c->stream));
+        AsClassify K{c->d_ip.p, c->d_as_hosts.p, c->d_as_flag.p, c->d_as_map.p, n, n_hosts, p.newest_host,
+                     p.current_min_act_dist, p.min_trace_quality, G};
+        k_ct_as_classify<<<nb, kCtThreads, 0, c->stream>>>(K, c->d_as_cand.p, c->d_as_disp.p, bin);
+        k_ct_sel_scan<<<1, kCtThreads, 0, c->stream>>>(bin, n_bins + 1, 1, cnt + kAsCntLive);
+        k_ct_as_scatter<<<nb, kCtThreads, 0, c->stream>>>(c->d_as_cand.p, c->d_as_disp.p, n, G, bin, cursor,
+                                                          c->d_as_entry.p);
+        // the rounds, a few launches between two looks at the count of the undecided: four at first (a
+        // candidate tries kAsAttempts times per launch), then eight at a time.  The corner pixel's candidates
+        // get one launch per batch: enough for the earliest undecided candidate to decide in every batch.
+        AsRound R{c->d_as_cand.p, c->d_as_entry.p, bin, c->d_as_map.p, c->d_as_disp.p, cnt, G, n_bins, 0};
+        for (int batches = 0, batch = 4;; batches++, batch = 8) {
+            if (batches > n + 1) return fail(-2, "the activation walk did not end (internal error)");  // each decides one
+            if (batches) HIP_TRY(hipMemsetAsync(cnt + kAsCntUndecided, 0, sizeof(int), c->stream));
+            for (int k = 0; k < batch; k++) {
+                R.count_undecided = k == batch - 1;
+                k_ct_as_round<<<nb, kCtThreads, 0, c->stream>>>(R);
+                if (k == batch - 1) k_ct_as_round_corner<<<1, kCtThreads, 0, c->stream>>>(R);
+            }
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(c->h_as_cnt.p, cnt, kAsCnts * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if (c->h_as_cnt.p[kAsCntUndecided] == 0) break;
+        }
+        AsOut O{c->d_ip.p, c->d_as_disp.p, c->d_as_blk.p, cnt, n, nb, n_hosts};
+        k_ct_as_count<<<nb, kCtThreads, 0, c->stream>>>(O);
+        k_ct_sel_scan<<<1, kCtThreads, 0, c->stream>>>(c->d_as_blk.p, nb, n_hosts + 1, c->d_as_tot.p);
+        k_ct_as_write<<<nb, kCtThreads, 0, c->stream>>>(O, c->d_as_tot.p, c->d_as_selected.p, c->d_as_out.p + n,
+                                                        compact ? c->d_ip_alt.p : nullptr, c->d_as_out.p,
+                                                        c->as_counts.dev);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c->h_as_out.p, c->d_as_out.p, 2 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // the counters are in mapped host memory
+        for (int k = 0; k < 4; k++) counts[k] = c->as_counts.p[k];
+        max_host = c->as_counts.p[kAsCntMaxHost] - 1;
+        if (disposition_out) std::memcpy(disposition_out, c->h_as_out.p, (size_t)n * sizeof(int));
+        if (selected_idx_out) std::memcpy(selected_idx_out, c->h_as_out.p + n, (size_t)counts[2] * sizeof(int));
+        if (compact) {
+            std::swap(c->d_ip.p, c->d_ip_alt.p);
+            std::swap(c->d_ip.n, c->d_ip_alt.n);
+            c->ip_n = counts[0];
+            c->ip_max_host = max_host;
+        }
+    }
+    c->as_sel_n = counts[2];
+    c->as_sel_hosts = n_hosts;
+    if (n_selected_out) *n_selected_out = counts[2];
+    if (counts_out) std::memcpy(counts_out, counts, sizeof counts);
+    return 0;
+}
+
+int ldso_ct_selection_download(ldso_ct_ctx *c, int32_t n, ldso_ct_immature *pts) {
+    if (!c) return fail(-1, "null context");
+    if (c->as_sel_n < 0) return fail(-1, "no selection: call ldso_ct_select_activation first");
+    if (n != c->as_sel_n) return fail(-1, "count differs from the selection");
+    if (n == 0) return 0;
+    if (!pts) return fail(-1, "null output");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(pts, c->d_as_selected.p, (size_t)n * sizeof(IpRec), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int ldso_ct_immature_append(ldso_ct_ctx *c, int32_t n, const ldso_ct_immature *pts) {
+    if (!c) return fail(-1, "null context");
+    if (n < 0 || (n > 0 && !pts)) return fail(-1, "bad point arguments");
+    int max_host = c->ip_max_host;
+    for (int k = 0; k < n; k++) {
+        if (pts[k].host < 0) return fail(-1, "immature point with a negative host index");
+        if (pts[k].last_status < 0 || pts[k].last_status > LDSO_CT_IPS_UNINITIALIZED)
+            return fail(-1, "immature point with an invalid status");
+        max_host = std::max(max_host, (int)pts[k].host);
+    }
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t need = (size_t)c->ip_n + n;
+    if (c->d_ip.n < need || !c->d_ip.p) {
+        // a larger buffer with room to spare, the resident records moved over on the device
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (int rc = c->d_ip_alt.alloc(std::max(need, 2 * c->d_ip.n))) return rc;
+        if (c->ip_n)
+            HIP_TRY(hipMemcpyAsync(c->d_ip_alt.p, c->d_ip.p, (size_t)c->ip_n * sizeof(IpRec), hipMemcpyDeviceToDevice,
+                                   c->stream));
+        std::swap(c->d_ip.p, c->d_ip_alt.p);
+        std::swap(c->d_ip.n, c->d_ip_alt.n);
+    }
+    HIP_TRY(hipMemcpyAsync(c->d_ip.p + c->ip_n, pts, (size_t)n * sizeof(IpRec), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->ip_n += n;
+    c->ip_max_host = max_host;
     return 0;
 }
 

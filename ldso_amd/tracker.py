@@ -18,8 +18,11 @@ Mirrors the reference class (src/frontend/CoarseTracker.cc) for the parts that r
     new ImmaturePoint(newFrame, feat, ..) -> make_immature(uv, type, host)     ImmaturePoint.cc:14-39
     traceNewCoarse -> ImmaturePoint::traceOn
                                           -> trace(krki, kt, aff)              FullSystem.cc:1157-1194,
-                                             (records resident: immature_upload / immature_download)
-                                                                               ImmaturePoint.cc:47-317
+                                             (records resident: immature_upload / immature_download /
+                                              immature_append)                 ImmaturePoint.cc:47-317
+    CoarseDistanceMap::makeDistanceMap    -> make_distance_map(krki1, kt1, uvd, host)
+                                             make_distance_map_ba(ba_ctx, win) CoarseTracker.cc:795-932
+    activatePointsMT's walk               -> select_activation(...)            FullSystem.cc:1220-1298
     PixelSelector(w, h)                   -> select_init(pattern, potential)   PixelSelector2.cc:9-18
     makeMaps(fh, map, density, ...)       -> select_pixels(density=..., ...)   PixelSelector2.cc:111-169
     makeNewTraces (pointSelection == 0)   -> make_new_traces(host, ...)        FullSystem.cc:1439-1461
@@ -272,6 +275,68 @@ class CoarseTracker:
         L.check(L.lib().ldso_ct_trace(self._h, int(krki.shape[0]), L.ptr(krki, L.f32p), L.ptr(kt, L.f32p),
                                       L.ptr(aff, L.f32p), L.ptr(c, L.i32p)))
         return c
+
+    def immature_append(self, pts: np.ndarray):
+        """More records behind the resident set (the new keyframe's)."""
+        assert pts.dtype == L.IMMATURE_DTYPE and pts.flags.c_contiguous
+        L.check(L.lib().ldso_ct_immature_append(self._h, int(pts.size), pts.ctypes.data))
+        self._ip_n = getattr(self, "_ip_n", 0) + int(pts.size)
+
+    # ---- activation candidates (CoarseDistanceMap, FullSystem::activatePointsMT's walk) ----
+    @property
+    def level1_shape(self):
+        return self.height >> 1, self.width >> 1
+
+    def make_distance_map(self, krki1, kt1, uvd, host, want_map: bool = True):
+        """makeDistanceMap from active points uvd [n][3] {u, v, idepth} with host [n] indexing the level-1
+        tables krki1 [n_hosts][9], kt1 [n_hosts][3] -> the map [h1, w1] (None without want_map)."""
+        krki1 = _f32(krki1).reshape(-1, 9)
+        kt1 = _f32(kt1).reshape(-1, 3)
+        uvd = _f32(uvd).reshape(-1, 3)
+        host = np.ascontiguousarray(host, np.int32).reshape(-1)
+        assert krki1.shape[0] == kt1.shape[0] and uvd.shape[0] == host.size
+        m = np.zeros(self.level1_shape, np.float32) if want_map else None
+        L.check(L.lib().ldso_ct_make_distance_map(self._h, int(krki1.shape[0]), L.ptr(krki1, L.f32p), L.ptr(kt1, L.f32p),
+                                                  int(host.size), L.ptr(uvd, L.f32p), L.ptr(host, L.i32p),
+                                                  L.ptr(m, L.f32p)))
+        return m
+
+    def make_distance_map_ba(self, ba_ctx, win: int, krki1, kt1, newest: int = -1, want_map: bool = True):
+        """The same with the points of a BAContext's window as seeds, device to device (newest -1: the
+        window's last frame)."""
+        krki1 = _f32(krki1).reshape(-1, 9)
+        kt1 = _f32(kt1).reshape(-1, 3)
+        assert krki1.shape[0] == kt1.shape[0]
+        m = np.zeros(self.level1_shape, np.float32) if want_map else None
+        L.check(L.lib().ldso_ct_make_distance_map_ba(self._h, ba_ctx._h, int(win), int(newest), L.ptr(krki1, L.f32p),
+                                                     L.ptr(kt1, L.f32p), L.ptr(m, L.f32p)))
+        return m
+
+    def select_activation(self, current_min_act_dist: float = 2.0, min_trace_quality: float = 3.0,
+                          newest_host: int = -2, flagged=None, compact: bool = False):
+        """activatePointsMT's walk over the resident records -> (dispositions [n] of _lib.ACT_*, the
+        OPTIMIZE records' indices in walk order, counts dict over _lib.ACTSEL_COUNTS).  newest_host -2:
+        the last host of the distance-map call.  compact: the resident set becomes the KEEP records."""
+        p = L.LdsoCtActselParams(float(current_min_act_dist), float(min_trace_quality), int(newest_host))
+        fl = None if flagged is None else np.ascontiguousarray(flagged, np.uint8).reshape(-1)
+        n = getattr(self, "_ip_n", 0)
+        disp = np.zeros(n, np.int32)
+        idx = np.zeros(n, np.int32)
+        ns = C.c_int32()
+        cnt = np.zeros(len(L.ACTSEL_COUNTS), np.int32)
+        L.check(L.lib().ldso_ct_select_activation(self._h, C.byref(p), L.ptr(fl, L.u8p), int(bool(compact)),
+                                                  L.ptr(disp, L.i32p), L.ptr(idx, L.i32p), C.byref(ns),
+                                                  L.ptr(cnt, L.i32p)))
+        self._as_sel_n = int(ns.value)
+        if compact:
+            self._ip_n = int(cnt[0])
+        return disp, idx[:ns.value].copy(), dict(zip(L.ACTSEL_COUNTS, cnt.tolist()))
+
+    def selection_download(self) -> np.ndarray:
+        """The records the last select_activation selected, in walk order."""
+        out = np.zeros(getattr(self, "_as_sel_n", 0), L.IMMATURE_DTYPE)
+        L.check(L.lib().ldso_ct_selection_download(self._h, int(out.size), out.ctypes.data))
+        return out
 
     # ---- pixel selection (PixelSelector::makeMaps, FullSystem::makeNewTraces with pointSelection 0) ----
     @staticmethod
