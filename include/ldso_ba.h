@@ -272,6 +272,10 @@ int ldso_ba_frame_put_device(ldso_ba_ctx *ctx, int64_t frame_id, const float *de
 /* The tracker's current new frame (ldso_ct_set_new_frame), level 0, device to device; the tracker's
  * next ldso_ct_set_new_frame is ordered after the ingest. */
 int ldso_ba_frame_put_tracker(ldso_ba_ctx *ctx, int64_t frame_id, const struct ldso_ct_ctx *tracker);
+/* The coarse initializer's first frame (the snapshot ldso_ct_init_set_first took of the tracker's new
+ * frame), level 0, device to device and event-ordered as ldso_ba_frame_put_tracker: the initializer's
+ * first keyframe needs no host dI. */
+int ldso_ba_frame_put_initializer(ldso_ba_ctx *ctx, int64_t frame_id, const struct ldso_ct_ctx *tracker);
 int ldso_ba_frame_drop(ldso_ba_ctx *ctx, int64_t frame_id);
 /* Read a resident frame back (test / debug; synchronises): intensity [h*w]; grad [h*w][2] only in
  * layout 1 (else it must be NULL). */

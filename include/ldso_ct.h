@@ -461,6 +461,132 @@ int ldso_ct_get_kernel_times(ldso_ct_ctx *ctx, double *ms, int64_t *counts, int3
 const char *ldso_ct_kernel_name(int32_t i);
 int32_t ldso_ct_num_kernels(void);
 
+/* ---- the coarse initializer: CoarseInitializer::trackFrame on the device ----------------------
+ *
+ *   CoarseInitializer::trackFrame      src/frontend/CoarseInitializer.cc:45-183  -> ldso_ct_init_track_frame
+ *     calcResAndGS, calculateAllResiduals, calculateAlphaEnergy, calculateSC  :186-518 -> ldso_ct_init_eval
+ *     one LM step of it on the host    :95-116                                -> ldso_ct_init_lm_step
+ *     calcEC, optReg, propagateUp / Down, resetPoints, doStep, applyStep      :520-631, 739-809
+ *   CoarseInitializer::setFirst        :656-737, the state it leaves          -> ldso_ct_init_set_first
+ *
+ * The points and their neighbour / parent tables go up once, at ldso_ct_init_set_first; every frame is
+ * then one call and one launch (one workgroup walks the levels and the LM iterations), and no image or
+ * point record comes back unless the caller asks (ldso_ct_init_get_points).  The first frame's pyramid
+ * is a device copy of the context's new frame, taken at set_first; ldso_ba_frame_put_initializer
+ * (include/ldso_ba.h) hands its level 0 to the BA frame store.
+ *
+ * Parity target: the reference's multiThreading == false branch.  The true branch adds per-thread
+ * accumulators in an order the scheduler picks and has no single answer: no parity claim.
+ * Types follow the reference: points, H, b, lambda and the increment are float, poses double, and
+ * SE3::exp(inc.head<6>().cast<double>()) is evaluated as written.  FP contraction is off.
+ * Every per-point statement is the reference's, bit for bit.  The float sums (accE, accEAlpha, the 45
+ * entries of acc9 and of acc9SC, calcEC's pair) have an order of this library's, the same in the loop
+ * and in ldso_ct_init_eval and repeatable run to run (ct_init.h: a lane adds its points i = lane, lane +
+ * 256, ... in order, each point's eight pattern terms first; a wave folds with the xor tree 32 ... 1;
+ * the four waves add in order); they are not the reference's blocked SSE order and are only bounded
+ * against it.  Two fixed-size Eigen reductions are written in their SSE packet order: doStep's
+ * JbBuffer.head<8>().dot(inc) and inc.norm(), p_k = a_k b_k + a_(k+4) b_(k+4), (p_0 + p_2) + (p_1 + p_3).
+ * Accumulator9::finish writes H(r, c) = H(c, r): both triangles of H and Hsc are filled, so Hl.ldlt()
+ * (LDLT<., Lower>) factorises the full symmetric system here (unlike the coarse tracker's Hl, whose
+ * lower triangle is empty).
+ * The two doors of ldso_ct_track: an accepted pose is kept as the matrix that was evaluated and becomes
+ * a quaternion again (Eigen's Quaternion(Matrix3)) for the next step, thisToNext is carried from call to
+ * call as that matrix, and SE3::exp's sine and cosine are the library's own on host and device.
+ * As in the reference, the LM loop tests `iteration >= max_iterations[lvl]` after a step: an entry of 0
+ * still runs one step per level.
+ * optReg and the top level's resetPoints are sequential in-place sweeps in the reference; here they run
+ * rank by rank (rank = 1 + the largest rank among the points of smaller index that are the point's
+ * neighbours or have it as a neighbour: kd-tree tables are not symmetric, and a point must also be swept
+ * before a later one that it reads), with a barrier between ranks: the result equals the sequential
+ * sweep for every input.  propagateUp adds each parent's children in child order.
+ *
+ * Not covered: setFirst's selection and makeNN (PixelSelector, makePixelStatus with its sparsityFactor,
+ * nanoflann's kd-tree) stay on the host -- ldso_ct_select_pixels gives level 0's map,
+ * ldso_ct_get_frame_level feeds makePixelStatus for the other levels, once per attempt; the inertial
+ * path; multiThreading == true; FullSystem::initializeFromInitializer.  Contexts of more than 5 pyramid
+ * levels are refused (maxIterations has five entries). */
+typedef struct ldso_ct_init_point {    /* Pnt (CoarseInitializer.h:23-57), the fields trackFrame touches */
+    float   u, v, idepth, ir, idepth_new;
+    float   energy[2], energy_new[2];
+    float   last_hessian, last_hessian_new, maxstep, outlier_th, my_type, ir_sum_num;
+    int32_t is_good, is_good_new;
+    int32_t parent;                    /* index in the next level; -1 on the top level */
+    int32_t neighbours[10];            /* -1: none */
+} ldso_ct_init_point;
+
+typedef struct ldso_ct_init_params {
+    float   alpha_k, alpha_w, reg_weight, coupling_weight;   /* 2.5^2, 150^2, 0.8, 1 */
+    int32_t max_iterations[5];         /* 5, 5, 10, 30, 50; each in [0, 1000] */
+    int32_t fix_affine;                /* fixAffine, 1 */
+    float   huber_th;                  /* setting_huberTH, 9 */
+} ldso_ct_init_params;
+void ldso_ct_init_default_params(ldso_ct_init_params *p);
+
+typedef struct ldso_ct_init_result {
+    double  this_to_next[12];          /* thisToNext (matrix3x4) */
+    double  this_to_next_aff[2];       /* thisToNext_aff */
+    float   latest_res[3];
+    int32_t snapped, frame_id, snapped_at;
+    int32_t ret;                       /* trackFrame's return value */
+    int32_t iterations[5];             /* LM steps per level */
+    float   phase_us[4];               /* where the launch's time went, by the workgroup's own clock: the
+                                          evaluations; the rank sweeps (optReg with propagateDown / Up, the top
+                                          level's resetPoints); the other per-point phases; lane 0's decisions */
+} ldso_ct_init_result;
+
+typedef struct ldso_ct_init_step {     /* one calcResAndGS of the loop, in program order */
+    double  pose[12], aff[2];          /* what was evaluated */
+    int32_t lvl, iteration;            /* iteration -1: the level's first evaluation */
+    int32_t accepted;                  /* iteration >= 0 only */
+    int32_t alpha_capped;              /* alphaOpt == 0 */
+    int32_t snapped;                   /* after this evaluation's decision */
+    float   lambda;                    /* the lambda the step was solved with (0 for iteration -1) */
+    float   inc[8];                    /* iteration >= 0 only */
+    float   res[3];                    /* calcResAndGS's return value */
+    float   reg_energy[3];             /* calcEC, iteration >= 0 only */
+} ldso_ct_init_step;
+
+/* setFirst's state from ready-made point lists (the caller's, as the ORB table is for
+ * ldso_ct_corners_init): snapshots every level of the context's new frame and its exposure as firstFrame,
+ * uploads pts_per_level[lvl][n_per_level[lvl]], resets thisToNext to the identity, thisToNext_aff to 0,
+ * snapped, frameID and snappedAt to 0.  Refused (< 0) with a message: no frame or ldso_ct_make_k, more
+ * than 5 levels, a level with n < 1, a neighbour that is neither -1 nor in range, a parent out of range
+ * of the next level (or not -1 on the top level), u or v not finite or closer than 2 pixels to the
+ * interpolable area's border (the pattern is read there without a check). */
+int ldso_ct_init_set_first(ldso_ct_ctx *ctx, const int32_t *n_per_level, const ldso_ct_init_point *const *pts_per_level);
+/* the list checks of ldso_ct_init_set_first alone (context-free), for a frame of width x height with
+ * `levels` pyramid levels */
+int ldso_ct_init_check_points(int32_t levels, int32_t width, int32_t height, const int32_t *n_per_level,
+                              const ldso_ct_init_point *const *pts_per_level);
+/* the records of level lvl as they stand; out may be NULL to query n */
+int ldso_ct_init_get_points(ldso_ct_ctx *ctx, int32_t lvl, ldso_ct_init_point *out, int32_t capacity, int32_t *n_out);
+/* overwrite the records of level lvl (n must be the level's count and the tables the resident ones):
+ * for a caller that replays or edits a state */
+int ldso_ct_init_set_points(ldso_ct_ctx *ctx, int32_t lvl, int32_t n, const ldso_ct_init_point *pts);
+/* One calcResAndGS on the resident points against the context's new frame: writes the _new fields, maxstep
+ * and JbBuffer_new as the reference does.  H, Hsc [8][8] row-major, b, bsc [8], res [3] = {E, alphaEnergy,
+ * num}; alpha_capped_out may be NULL.  Bitwise what the loop of ldso_ct_init_track_frame computes at the
+ * same pose and point state.  params NULL: the defaults. */
+int ldso_ct_init_eval(ldso_ct_ctx *ctx, int32_t lvl, const double ref_to_new[12], const double aff[2],
+                      const ldso_ct_init_params *params, float H[64], float b[8], float Hsc[64], float bsc[8],
+                      float res[3], int32_t *alpha_capped_out);
+/* lines :95-116 on the host with the statements the kernel runs (context-free): the damped, Schur-reduced,
+ * wM-scaled float system, Hl.ldlt() in float (the 6x6 corner with fix_affine), exp(inc) * pose.  w, h: the
+ * level's image size. */
+int ldso_ct_init_lm_step(const float H[64], const float b[8], const float Hsc[64], const float bsc[8], float lambda,
+                         int32_t w, int32_t h, const double pose[12], const double aff[2],
+                         const ldso_ct_init_params *params, float inc_out[8], double pose_out[12], double aff_out[2]);
+/* optReg(lvl) alone on the resident points, as if snapped were `snapped` */
+int ldso_ct_init_opt_reg(ldso_ct_ctx *ctx, int32_t lvl, float reg_weight, int32_t snapped);
+/* trackFrame on the context's new frame: one launch.  trace (may be NULL): every evaluation, at most
+ * trace_capacity; *trace_n = how many there were (may be NULL).  params NULL: the defaults.
+ * Refused: no ldso_ct_init_set_first, non-finite or non-positive params, iteration counts outside
+ * [0, 1000], trace with trace_capacity < 1. */
+int ldso_ct_init_track_frame(ldso_ct_ctx *ctx, const ldso_ct_init_params *params, ldso_ct_init_result *result,
+                             ldso_ct_init_step *trace, int32_t trace_capacity, int32_t *trace_n);
+/* ranks of the sweep per level (ldso_ct_init_set_first computed them): out [levels] */
+int ldso_ct_init_rank_counts(ldso_ct_ctx *ctx, int32_t *out);
+
 #ifdef __cplusplus
 }
 #endif

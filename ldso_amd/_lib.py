@@ -212,6 +212,7 @@ ABI = [
     ("ldso_ba_frame_put", C.c_int, [C.c_void_p, C.c_int64, f32p]),
     ("ldso_ba_frame_put_device", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ldso_ba_frame_put_tracker", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    ("ldso_ba_frame_put_initializer", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     ("ldso_ba_frame_drop", C.c_int, [C.c_void_p, C.c_int64]),
     ("ldso_ba_frame_get", C.c_int, [C.c_void_p, C.c_int64, f32p, f32p]),
     ("ldso_ba_load_frames", C.c_int, [C.c_void_p, C.c_int32, C.POINTER(LdsoBaWindow), i64p, C.c_int32, C.c_int32]),
@@ -272,6 +273,33 @@ FEATURE_DTYPE = np.dtype([("score", "<f4"), ("angle", "<f4"), ("is_corner", "<i4
 assert FEATURE_DTYPE.itemsize == 48
 CORNER_STATS = ("gridsize", "k", "candidates", "features", "corners", "max_score_bits")  # LDSO_CT_CORNER_STATS
 
+
+
+class LdsoCtInitParams(C.Structure):
+    """ldso_ct_init_params (include/ldso_ct.h)"""
+    _fields_ = [("alpha_k", C.c_float), ("alpha_w", C.c_float), ("reg_weight", C.c_float),
+                ("coupling_weight", C.c_float), ("max_iterations", C.c_int32 * 5), ("fix_affine", C.c_int32),
+                ("huber_th", C.c_float)]
+
+
+# ldso_ct_init_point / _result / _step (include/ldso_ct.h): the coarse initializer's records
+INIT_POINT_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("idepth", "<f4"), ("ir", "<f4"), ("idepth_new", "<f4"),
+                             ("energy", "<f4", (2,)), ("energy_new", "<f4", (2,)), ("last_hessian", "<f4"),
+                             ("last_hessian_new", "<f4"), ("maxstep", "<f4"), ("outlier_th", "<f4"),
+                             ("my_type", "<f4"), ("ir_sum_num", "<f4"), ("is_good", "<i4"), ("is_good_new", "<i4"),
+                             ("parent", "<i4"), ("neighbours", "<i4", (10,))])
+INIT_RESULT_DTYPE = np.dtype([("this_to_next", "<f8", (12,)), ("this_to_next_aff", "<f8", (2,)),
+                              ("latest_res", "<f4", (3,)), ("snapped", "<i4"), ("frame_id", "<i4"),
+                              ("snapped_at", "<i4"), ("ret", "<i4"), ("iterations", "<i4", (5,)),
+                              ("phase_us", "<f4", (4,))], align=True)
+INIT_PHASES = ("evaluations", "rank_sweeps", "point_phases", "lane0")  # ldso_ct_init_result.phase_us
+INIT_STEP_DTYPE = np.dtype([("pose", "<f8", (12,)), ("aff", "<f8", (2,)), ("lvl", "<i4"), ("iteration", "<i4"),
+                            ("accepted", "<i4"), ("alpha_capped", "<i4"), ("snapped", "<i4"), ("lambda", "<f4"),
+                            ("inc", "<f4", (8,)), ("res", "<f4", (3,)), ("reg_energy", "<f4", (3,))], align=True)
+assert INIT_POINT_DTYPE.itemsize == 112 and INIT_RESULT_DTYPE.itemsize == 176 and INIT_STEP_DTYPE.itemsize == 192
+assert C.sizeof(LdsoCtInitParams) == 44
+init_point_pp = C.POINTER(C.c_void_p)
+
 # (name, restype, argtypes) of every entry point declared in include/ldso_ct.h (coarse tracker)
 CT_ABI = [
     ("ldso_ct_create", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), i32p]),
@@ -313,6 +341,17 @@ CT_ABI = [
     ("ldso_ct_corners_init", C.c_int, [C.c_void_p, i32p]),
     ("ldso_ct_detect_corners", C.c_int,
      [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, i32p, i32p]),
+    ("ldso_ct_init_default_params", None, [C.c_void_p]),
+    ("ldso_ct_init_check_points", C.c_int, [C.c_int32, C.c_int32, C.c_int32, i32p, init_point_pp]),
+    ("ldso_ct_init_set_first", C.c_int, [C.c_void_p, i32p, init_point_pp]),
+    ("ldso_ct_init_get_points", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, i32p]),
+    ("ldso_ct_init_set_points", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    ("ldso_ct_init_eval", C.c_int, [C.c_void_p, C.c_int32, f64p, f64p, C.c_void_p, f32p, f32p, f32p, f32p, f32p, i32p]),
+    ("ldso_ct_init_lm_step", C.c_int, [f32p, f32p, f32p, f32p, C.c_float, C.c_int32, C.c_int32, f64p, f64p,
+                                       C.c_void_p, f32p, f64p, f64p]),
+    ("ldso_ct_init_opt_reg", C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_int32]),
+    ("ldso_ct_init_track_frame", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, i32p]),
+    ("ldso_ct_init_rank_counts", C.c_int, [C.c_void_p, i32p]),
     ("ldso_ct_set_kernel_timing", C.c_int, [C.c_void_p, C.c_int32]),
     ("ldso_ct_get_kernel_times", C.c_int, [C.c_void_p, f64p, i64p, C.c_int32]),
     ("ldso_ct_kernel_name", C.c_char_p, [C.c_int32]),

@@ -125,6 +125,11 @@ class BAContext:
         """The tracker's current new frame (CoarseTracker.set_new_frame), device to device."""
         L.check(self._lib.ldso_ba_frame_put_tracker(self._h, int(frame_id), tracker._h))
 
+    def frame_put_initializer(self, frame_id: int, tracker):
+        """The coarse initializer's first frame (the snapshot CoarseInitializer.set_first took), device to
+        device.  tracker: a CoarseTracker or the CoarseInitializer on it."""
+        L.check(self._lib.ldso_ba_frame_put_initializer(self._h, int(frame_id), tracker._h))
+
     def frame_drop(self, frame_id: int):
         L.check(self._lib.ldso_ba_frame_drop(self._h, int(frame_id)))
 

@@ -15,6 +15,7 @@
 #include "k_ct_corners.h"
 #include "k_ct_track.h"
 #include "k_ct_actsel.h"
+#include "k_ct_init.h"
 
 namespace {
 
@@ -121,6 +122,27 @@ struct ldso_ct_ctx {
     DevBuf<IpRec> d_as_selected, d_ip_alt;
     int as_sel_n = -1, as_sel_hosts = 0;    // -1: no selection yet
     Event as_ev_a, as_ev_b;
+    // the coarse initializer (k_ct_init.h): firstFrame's pyramid and level-0 intensities, snapshots of the
+    // new frame at ldso_ct_init_set_first; the points of every level back to back; the sweep orders, rank
+    // offsets and child lists, one int table; JbBuffer | JbBuffer_new; the state trackFrame carries from
+    // call to call; result, evaluation and trace in mapped host memory
+    DevBuf<float4> d_init_first;
+    DevBuf<float> d_init_inten;
+    DevBuf<ldso_ct_init_point> d_init_pts;
+    DevBuf<int> d_init_tab;
+    DevBuf<float> d_init_jb;
+    PinMappedOf<CtInitOut> init_out;
+    PinMappedOf<ldso_ct_init_step> init_trace;
+    bool init_have_first = false;
+    int init_off[ldso_ct::kInitMaxLevels + 1] = {0};
+    int init_order_off[ldso_ct::kInitMaxLevels] = {0}, init_rank_off[ldso_ct::kInitMaxLevels] = {0};
+    int init_child_off[ldso_ct::kInitMaxLevels] = {0}, init_child[ldso_ct::kInitMaxLevels] = {0};
+    int init_n_ranks[ldso_ct::kInitMaxLevels] = {0};
+    int init_max_n = 0, init_jb_cur = 0;
+    float init_first_exposure = 0;
+    double init_this_to_next[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    float init_aff[2] = {0, 0};
+    int init_snapped = 0, init_frame_id = 0, init_snapped_at = 0;
     // kernel timing, on events with the default flags
     KernelTimer<kNumCtKernels> timer{hipEventDefault, kCtKernelNames};
 };

@@ -633,6 +633,22 @@ int ldso_ba_frame_put_tracker(ldso_ba_ctx *c, int64_t frame_id, const ldso_ct_ct
     return store_ingest_device(c, frame_id, v.intensity, v.texels, static_cast<hipStream_t>(v.stream));
 }
 
+int ldso_ba_frame_put_initializer(ldso_ba_ctx *c, int64_t frame_id, const ldso_ct_ctx *tracker) {
+    if (!c || !tracker) return fail(-1, "null argument");
+    const ImageLayout &l = c->store.lay;
+    if (c->store.cap == 0) return fail(LDSO_BA_ERR_FRAME_STORE, "no frame store: call ldso_ba_frames_reserve first");
+    ldso_ba::CtFrameView v{};
+    int rc = ldso_ba::ct_init_frame_view(tracker, &v);
+    if (rc) return rc;
+    if (v.device != c->device) return fail(-1, "tracker and context are on different devices");
+    if (v.width != l.width || v.height != l.height)
+        return fail(LDSO_BA_ERR_FRAME_STORE, "the initializer's first frame is " + std::to_string(v.width) + "x" +
+                                                 std::to_string(v.height) + ", the frame store holds " +
+                                                 std::to_string(l.width) + "x" + std::to_string(l.height));
+    if (!v.have_frame) return fail(-1, "the tracker has no first frame: ldso_ct_init_set_first not called");
+    return store_ingest_device(c, frame_id, v.intensity, v.texels, static_cast<hipStream_t>(v.stream));
+}
+
 int ldso_ba_frame_drop(ldso_ba_ctx *c, int64_t frame_id) {
     if (!c) return fail(-1, "null ctx");
     const int s = c->store.find(frame_id);

@@ -107,6 +107,9 @@ struct CtFrameView {
     bool have_frame;  // ldso_ct_set_new_frame has run
 };
 int ct_frame_view(const ldso_ct_ctx *ct, CtFrameView *out);
+// the same view of the coarse initializer's first frame, the snapshot ldso_ct_init_set_first took
+// (ldso_ba_frame_put_initializer); have_frame: set_first has run
+int ct_init_frame_view(const ldso_ct_ctx *ct, CtFrameView *out);
 
 // The mirror image: one window of a BA context as the coarse tracker reads it after a pass
 // (ldso_ct_make_reference_ba; the tracker translation unit does not see ldso_ba_ctx).  Every

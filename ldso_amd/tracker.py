@@ -31,6 +31,13 @@ Mirrors the reference class (src/frontend/CoarseTracker.cc) for the parts that r
                                           -> detect_corners(n_features, host)  FeatureDetector.cc:34-189,
                                                                                FullSystem.cc:1428-1438
 
+CoarseInitializer (src/frontend/CoarseInitializer.cc) on a tracker's frames:
+
+    setFirst's state from ready-made lists -> CoarseInitializer(tracker).set_first(levels)   :656-737
+    trackFrame(newFrame)                  -> track_frame(...)                  :45-183
+    calcResAndGS                          -> eval(lvl, T, aff)                 :186-342
+    the LM step                           -> init_lm_step(H, b, Hsc, bsc, ...) :95-116
+
 No numerical work happens here; every call goes to libldso_ba.so (no fallback).
 """
 from __future__ import annotations
@@ -416,3 +423,105 @@ class CoarseTracker:
             cap = int(n.value)
         L.check(rc)
         return rec[:n.value].copy(), feat[:n.value].copy(), dict(zip(L.CORNER_STATS, st.tolist()))
+
+
+def init_params(**params) -> "L.LdsoCtInitParams":
+    """ldso_ct_init_params: the defaults with the given fields replaced (max_iterations: 5 ints)."""
+    p = L.LdsoCtInitParams()
+    L.lib().ldso_ct_init_default_params(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(p._fields_):
+            raise TypeError(f"unknown initializer parameter {k!r}")
+        setattr(p, k, (C.c_int32 * 5)(*v) if k == "max_iterations" else v)
+    return p
+
+
+def _point_lists(levels):
+    levels = [np.ascontiguousarray(lv, L.INIT_POINT_DTYPE) for lv in levels]
+    n = np.array([lv.size for lv in levels], np.int32)
+    pp = (C.c_void_p * len(levels))(*[lv.ctypes.data for lv in levels])
+    return levels, n, pp
+
+
+def init_check_points(levels, width: int, height: int):
+    """The list checks of set_first alone (ldso_ct_init_check_points); raises LdsoError on a bad list."""
+    keep, n, pp = _point_lists(levels)
+    L.check(L.lib().ldso_ct_init_check_points(len(keep), int(width), int(height), L.ptr(n, L.i32p), pp))
+
+
+def init_lm_step(H, b, Hsc, bsc, lam: float, w: int, h: int, ref_to_new, aff_ab, **params):
+    """Lines :95-116 of trackFrame on the host (ldso_ct_init_lm_step) -> (inc [8] float32, pose [3][4], aff [2])."""
+    f = [np.ascontiguousarray(x, np.float32).reshape(-1) for x in (H, b, Hsc, bsc)]
+    T = np.ascontiguousarray(np.asarray(ref_to_new, np.float64)[:3, :4])
+    ab = np.ascontiguousarray(aff_ab, np.float64).reshape(2)
+    inc, To, abo = np.zeros(8, np.float32), np.zeros((3, 4)), np.zeros(2)
+    p = init_params(**params)
+    L.check(L.lib().ldso_ct_init_lm_step(*[L.ptr(x, L.f32p) for x in f], float(lam), int(w), int(h), L.ptr(T, L.f64p),
+                                         L.ptr(ab, L.f64p), C.byref(p), L.ptr(inc, L.f32p), L.ptr(To, L.f64p),
+                                         L.ptr(abo, L.f64p)))
+    return inc, To, abo
+
+
+class CoarseInitializer:
+    """CoarseInitializer on the frames of a CoarseTracker: the tracker's new frame at set_first is
+    firstFrame, every later new frame is trackFrame's newFrame."""
+
+    def __init__(self, tracker: CoarseTracker):
+        self.tracker = tracker
+        self._h = tracker._h
+        self.levels = tracker.levels
+
+    def set_first(self, levels):
+        """levels: per pyramid level an array of _lib.INIT_POINT_DTYPE (points with their neighbour and
+        parent tables, as setFirst and makeNN leave them)."""
+        keep, n, pp = _point_lists(levels)
+        assert len(keep) == self.levels
+        L.check(L.lib().ldso_ct_init_set_first(self._h, L.ptr(n, L.i32p), pp))
+        self._n = n.copy()
+
+    def points(self, lvl: int) -> np.ndarray:
+        n = C.c_int32()
+        lib = L.lib()
+        L.check(lib.ldso_ct_init_get_points(self._h, int(lvl), None, 0, C.byref(n)))
+        out = np.zeros(n.value, L.INIT_POINT_DTYPE)
+        L.check(lib.ldso_ct_init_get_points(self._h, int(lvl), out.ctypes.data, int(n.value), C.byref(n)))
+        return out
+
+    def set_points(self, lvl: int, pts: np.ndarray):
+        pts = np.ascontiguousarray(pts, L.INIT_POINT_DTYPE)
+        L.check(L.lib().ldso_ct_init_set_points(self._h, int(lvl), int(pts.size), pts.ctypes.data))
+
+    def rank_counts(self) -> np.ndarray:
+        out = np.zeros(self.levels, np.int32)
+        L.check(L.lib().ldso_ct_init_rank_counts(self._h, L.ptr(out, L.i32p)))
+        return out
+
+    def eval(self, lvl: int, ref_to_new, aff_ab=(0.0, 0.0), **params):
+        """One calcResAndGS on the resident points -> (H [8][8], b [8], Hsc [8][8], bsc [8], res [3],
+        alpha capped), float32."""
+        T = np.ascontiguousarray(np.asarray(ref_to_new, np.float64)[:3, :4])
+        ab = np.ascontiguousarray(aff_ab, np.float64).reshape(2)
+        H, b, Hsc, bsc, res = (np.zeros(s, np.float32) for s in ((8, 8), 8, (8, 8), 8, 3))
+        capped = C.c_int32()
+        p = init_params(**params)
+        L.check(L.lib().ldso_ct_init_eval(self._h, int(lvl), L.ptr(T, L.f64p), L.ptr(ab, L.f64p), C.byref(p),
+                                          L.ptr(H, L.f32p), L.ptr(b, L.f32p), L.ptr(Hsc, L.f32p), L.ptr(bsc, L.f32p),
+                                          L.ptr(res, L.f32p), C.byref(capped)))
+        return H, b, Hsc, bsc, res, bool(capped.value)
+
+    def opt_reg(self, lvl: int, reg_weight: float = 0.8, snapped: bool = True):
+        L.check(L.lib().ldso_ct_init_opt_reg(self._h, int(lvl), float(reg_weight), int(bool(snapped))))
+
+    def track_frame(self, trace: int = 0, **params):
+        """trackFrame on the tracker's new frame, one launch -> the result record (_lib.INIT_RESULT_DTYPE), and
+        with trace > 0 also the first `trace` evaluations (_lib.INIT_STEP_DTYPE) and how many there were."""
+        p = init_params(**params)
+        out = np.zeros(1, L.INIT_RESULT_DTYPE)
+        steps = np.zeros(max(int(trace), 0), L.INIT_STEP_DTYPE)
+        n_steps = C.c_int32()
+        L.check(L.lib().ldso_ct_init_track_frame(self._h, C.byref(p), out.ctypes.data,
+                                                 steps.ctypes.data if steps.size else None, int(steps.size),
+                                                 C.byref(n_steps)))
+        if trace > 0:
+            return out[0], steps[:min(n_steps.value, steps.size)].copy(), int(n_steps.value)
+        return out[0]
