@@ -21,6 +21,9 @@
  *
  *   CoarseTracker::trackNewestCoarse    src/frontend/CoarseTracker.cc:61-310  -> ldso_ct_track
  *     one LM step of it on the host                                            (+ ldso_ct_lm_step)
+ *   Undistort::undistort                src/frontend/Undistort.cc:190-230, 398-453 -> ldso_ct_set_new_frame_raw
+ *     from the raw 8- / 16-bit image, makeImages behind it                     (+ _device; the tables' host
+ *                                                                              helpers ldso_ct_undistort_make_*)
  *
  * The reference frame's point cloud (pc_u/pc_v/pc_idepth/pc_color per pyramid level) is built on
  * the device by ldso_ct_make_reference / ldso_ct_make_reference_ba, or handed over ready-made by
@@ -586,6 +589,89 @@ int ldso_ct_init_track_frame(ldso_ct_ctx *ctx, const ldso_ct_init_params *params
                              ldso_ct_init_step *trace, int32_t trace_capacity, int32_t *trace_n);
 /* ranks of the sweep per level (ldso_ct_init_set_first computed them): out [levels] */
 int ldso_ct_init_rank_counts(ldso_ct_ctx *ctx, int32_t *out);
+
+/* ---- frame ingestion: Undistort::undistort from the raw image (src/frontend/Undistort.cc) ----
+ *
+ *   PhotometricUndistorter::processFrame   Undistort.cc:190-230  \  one launch, k_ct_undistort, into the
+ *   Undistort::undistort's remap loop      Undistort.cc:398-453  /  image ldso_ct_set_new_frame uploads
+ *   Undistort::readFromFile's numeric part Undistort.cc:738-751, 802-868  -> ldso_ct_undistort_make_remap
+ *   Undistort::makeOptimalK_crop           Undistort.cc:558-668              (host, no context)
+ *   distortCoordinates of the five models  Undistort.cc:891-1125
+ *   PhotometricUndistorter's tables        Undistort.cc:86-103, 120-154   -> ldso_ct_undistort_make_photometric
+ *
+ * A raw 8- or 16-bit frame goes to the device as the camera delivered it; the ImageAndExposure float
+ * image, the pyramid and the BA frame store never exist on the host.  The image is the reference's bit
+ * for bit (contraction off, every float statement in the reference's order); a NaN's sign and payload
+ * are not part of that claim.
+ *
+ * The footprint rule.  The reference keeps a remap entry when iy < wOrg - 1 (Undistort.cc:860 tests the
+ * width), so with hOrg < wOrg its blend reads past the source image.  As everywhere in this library the
+ * reference's reads outside an array are not reproduced: ldso_ct_undistort_init stores an entry as
+ * (-1, -1), whose output pixel is 0, when it is not finite or when its 2 x 2 footprint
+ * [xxi, xxi + 1] x [yyi, yyi + 1] (xxi = (int)xx, yyi = (int)yy) is not inside the w_org x h_org source,
+ * and counts it.  An entry with xx < 0 is the reference's own "write 0" mark: it is kept and not counted.
+ * Nothing is ever read outside the source.
+ *
+ * Not built: the parsing of the calibration text, the photometric text and the vignette image (the
+ * caller hands over numbers); benchmark_varNoise / benchmark_varBlurNoise (Undistort.cc:384-421,
+ * 469-556), which draw from rand(); benchmarkSetting_* overrides; PhotometricUndistorter::unMapFloatImage;
+ * makeOptimalK_full, where the reference asserts false. */
+typedef struct ldso_ct_undistort_desc {
+    int32_t w_org, h_org;       /* the raw image's size (>= 2 x 2) */
+    const float *remap_x;       /* [height*width] at the context's size, source coordinates; both NULL: */
+    const float *remap_y;       /*   passthrough (Undistort.cc:451-453), which needs w_org x h_org == the context's size */
+    const float *g;             /* [g_depth] the response LUT G; NULL: no photometric calibration (valid == false) */
+    int32_t g_depth;            /* >= 256 with g */
+    const float *vignette_inv;  /* [h_org*w_org] vignetteMapInv; required with g (valid needs both) */
+    int32_t photometric_mode;   /* setting_photometricCalibration: 0 factor * raw, 1 G[raw], 2 G[raw] * vignette_inv */
+    int32_t use_exposure;       /* setting_useExposure */
+} ldso_ct_undistort_desc;
+
+/* The tables go to the device once.  n_outside_out (may be NULL): the entries the footprint rule stored
+ * as -1.  Refused: null arguments, sizes below 2 x 2, g_depth < 256, g without vignette_inv, one remap
+ * pointer without the other, passthrough with differing sizes, a mode outside 0..2. */
+int ldso_ct_undistort_init(ldso_ct_ctx *ctx, const ldso_ct_undistort_desc *d, int32_t *n_outside_out);
+/* Undistort::undistort(raw, exposure_time, ., factor) and makeImages of its image: raw [h_org*w_org] of
+ * bits = 8 (uint8_t) or 16 (uint16_t) through pinned staging, k_ct_undistort, then the pyramid launches
+ * of ldso_ct_set_new_frame.  *exposure_out (may be NULL): ImageAndExposure::exposure_time, that is
+ * exposure_time, or 1 without use_exposure; it also becomes the new frame's ab_exposure.  factor applies
+ * where the reference takes its first branch (no g, exposure_time <= 0 or mode 0).  Refused: before
+ * ldso_ct_undistort_init; bits other than 8 / 16; 16 bits on the LUT branch unless g_depth == 65536. */
+int ldso_ct_set_new_frame_raw(ldso_ct_ctx *ctx, const void *raw, int32_t bits, float exposure_time, float factor,
+                              const float *b_response, float *exposure_out);
+/* The same from device memory (a torch tensor, a capture card's DMA target) produced on producer_stream
+ * (hipStream_t; NULL: the null stream): ordered by events in both directions, no host synchronisation,
+ * as ldso_ba_frame_put_device.  dev_raw must stay alive until the stream work has run. */
+int ldso_ct_set_new_frame_raw_device(ldso_ct_ctx *ctx, const void *dev_raw, int32_t bits, float exposure_time,
+                                     float factor, const float *b_response, void *producer_stream,
+                                     float *exposure_out);
+/* the level-0 image of the new frame (either entry point's) as [height*width]: ImageAndExposure::image for
+ * callers that still need it on the host (setting_pointSelection == 2, display) */
+int ldso_ct_get_undistorted(ldso_ct_ctx *ctx, float *image);
+
+enum { LDSO_CT_UNDISTORT_FOV = 0, LDSO_CT_UNDISTORT_RADTAN = 1, LDSO_CT_UNDISTORT_EQUIDISTANT = 2,
+       LDSO_CT_UNDISTORT_KANNALA_BRANDT = 3, LDSO_CT_UNDISTORT_PINHOLE = 4 };
+enum { LDSO_CT_UNDISTORT_OUT_CROP = 0, LDSO_CT_UNDISTORT_OUT_NONE = 1, LDSO_CT_UNDISTORT_OUT_CALIB = 2,
+       LDSO_CT_UNDISTORT_OUT_FULL = 3 /* refused: the reference asserts false */ };
+/* Host, no context: the remap tables and the rectified K the reference's Undistort constructor leaves.
+ * pars: parsOrg as read from the first line {fx, fy, cx, cy, then omega (FOV) or four distortion
+ * coefficients}; the relative format (cx < 1 and cy < 1) is rescaled as the reference does.  out_mode
+ * CALIB: out_calib = the third line's {fx, fy, cx, cy}, relative to the output size (else may be NULL).
+ * K_out: {fx, fy, cx, cy} of K, double as the reference's Mat33.  remap_x / remap_y [h*w]: the tables after
+ * the "rounding resistant" pass, kept verbatim (iy == hOrg - 1 sets ix; the bound on iy is wOrg - 1), so
+ * they are the reference's; ldso_ct_undistort_init applies the footprint rule.  *passthrough_out: 1 for
+ * OUT_NONE (the tables are still written).  tanf / atanf / atan2f / sqrtf are the host libm's.
+ * Refused: null arguments, an unknown model or mode, OUT_FULL, sizes below 2 x 2, OUT_NONE with differing
+ * sizes, a crop search that does not end within 500 rounds (the reference exits). */
+int ldso_ct_undistort_make_remap(int32_t model, const double pars[8], int32_t w_org, int32_t h_org, int32_t w, int32_t h,
+                                 int32_t out_mode, const float out_calib[4], double K_out[4], float *remap_x,
+                                 float *remap_y, int32_t *passthrough_out);
+/* Host, no context: G [g_depth] and vignetteMapInv [n] from the numbers of the photometric text's first
+ * line and the vignette image's pixels (vignette_bits 8: uint8_t, 16: uint16_t).  G: strictly increasing or
+ * refused; 255.0 * (G[i] - min) / (max - min) in the reference's float / double mix; mode 0: the ramp
+ * 255.0f * i / (g_depth - 1).  vignette_inv_out = 1.0f / (v / maxV): a zero pixel gives inf, which is kept. */
+int ldso_ct_undistort_make_photometric(const float *g_raw, int32_t g_depth, const void *vignette, int32_t vignette_bits,
+                                       int32_t n, int32_t photometric_mode, float *g_out, float *vignette_inv_out);
 
 #ifdef __cplusplus
 }

@@ -282,6 +282,16 @@ class LdsoCtInitParams(C.Structure):
                 ("huber_th", C.c_float)]
 
 
+class LdsoCtUndistortDesc(C.Structure):
+    """ldso_ct_undistort_desc (include/ldso_ct.h)"""
+    _fields_ = [("w_org", C.c_int32), ("h_org", C.c_int32), ("remap_x", f32p), ("remap_y", f32p), ("g", f32p),
+                ("g_depth", C.c_int32), ("vignette_inv", f32p), ("photometric_mode", C.c_int32),
+                ("use_exposure", C.c_int32)]
+
+
+UNDISTORT_MODELS = ("fov", "radtan", "equidistant", "kannala_brandt", "pinhole")  # LDSO_CT_UNDISTORT_*
+UNDISTORT_OUT = ("crop", "none", "calib", "full")  # LDSO_CT_UNDISTORT_OUT_*
+
 # ldso_ct_init_point / _result / _step (include/ldso_ct.h): the coarse initializer's records
 INIT_POINT_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("idepth", "<f4"), ("ir", "<f4"), ("idepth_new", "<f4"),
                              ("energy", "<f4", (2,)), ("energy_new", "<f4", (2,)), ("last_hessian", "<f4"),
@@ -352,6 +362,15 @@ CT_ABI = [
     ("ldso_ct_init_opt_reg", C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_int32]),
     ("ldso_ct_init_track_frame", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, i32p]),
     ("ldso_ct_init_rank_counts", C.c_int, [C.c_void_p, i32p]),
+    ("ldso_ct_undistort_init", C.c_int, [C.c_void_p, C.c_void_p, i32p]),
+    ("ldso_ct_set_new_frame_raw", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, f32p, f32p]),
+    ("ldso_ct_set_new_frame_raw_device", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, f32p, C.c_void_p, f32p]),
+    ("ldso_ct_get_undistorted", C.c_int, [C.c_void_p, f32p]),
+    ("ldso_ct_undistort_make_remap", C.c_int, [C.c_int32, f64p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                               f32p, f64p, f32p, f32p, i32p]),
+    ("ldso_ct_undistort_make_photometric", C.c_int, [f32p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                     f32p, f32p]),
     ("ldso_ct_set_kernel_timing", C.c_int, [C.c_void_p, C.c_int32]),
     ("ldso_ct_get_kernel_times", C.c_int, [C.c_void_p, f64p, i64p, C.c_int32]),
     ("ldso_ct_kernel_name", C.c_char_p, [C.c_int32]),

@@ -16,6 +16,7 @@
 #include "k_ct_track.h"
 #include "k_ct_actsel.h"
 #include "k_ct_init.h"
+#include "k_ct_undistort.h"
 
 namespace {
 
@@ -143,6 +144,16 @@ struct ldso_ct_ctx {
     double init_this_to_next[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     float init_aff[2] = {0, 0};
     int init_snapped = 0, init_frame_id = 0, init_snapped_at = 0;
+    // frame ingestion (k_ct_undistort.h): the tables of ldso_ct_undistort_init; the raw frame's pinned and
+    // device staging, sized for 16 bits; the events that order a device source's stream with the context's
+    DevBuf<float2> d_und_remap;
+    DevBuf<float> d_und_g, d_und_vinv;
+    bool und_init = false, und_pass = false;
+    int und_w_org = 0, und_h_org = 0, und_g_depth = 0;  // g_depth 0: no photometric calibration
+    int und_mode = 0, und_use_exposure = 1;
+    PinBuf<uint8_t> h_und_raw;
+    DevBuf<uint8_t> d_und_raw;
+    Event und_ev_prod, und_ev_cons;
     // kernel timing, on events with the default flags
     KernelTimer<kNumCtKernels> timer{hipEventDefault, kCtKernelNames};
 };

@@ -9,7 +9,8 @@
 //   k_ct_track.h         k_ct_track: trackNewestCoarse's LM loop, one launch (ct_lm.h: the loop's host/device half)
 //   k_ct_init.h          k_ct_init_track, k_ct_init_eval, k_ct_init_opt_reg: CoarseInitializer::trackFrame, one launch
 //                        (ct_init.h: the loop's host/device half)
-//   ct_context.h         the timing slots and struct ldso_ct_ctx
+//   k_ct_undistort.h     k_ct_undistort: the new frame's image from the raw 8- / 16-bit one (Undistort::undistort)
+//   ct_context.h        the timing slots and struct ldso_ct_ctx
 //   hip_owning.h         shared with ldso_ba.hip: fail / HIP_TRY, the owning buffers and events, KernelTimer
 #include <hip/hip_runtime.h>
 
@@ -29,6 +30,7 @@
 #include "k_ct_coarse_depth.h"
 #include "k_ct_track.h"
 #include "k_ct_actsel.h"
+#include "k_ct_undistort.h"
 #include "ct_context.h"
 
 #pragma clang fp contract(off)
@@ -562,6 +564,64 @@ int track_check_params(const ldso_ct_track_params &p) {
     return 0;
 }
 
+// ---- the new frame (k_ct_pyramid.h, k_ct_undistort.h) --------------------------------------------
+// makeImages behind a level-0 image in d_color: the response table's upload and the two pyramid launches
+// on the context's stream, no synchronisation.  Both ways of setting the new frame end here.
+int frame_pyramid(ldso_ct_ctx *c, const float *b_response) {
+    const PyrParams &P = c->pyr;
+    if (b_response)
+        HIP_TRY(hipMemcpyAsync(c->d_B.p, b_response, 256 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    const float *B = b_response ? c->d_B.p : nullptr;
+    const dim3 grid(P.w / P.tile, P.h / P.tile);
+    const size_t lds = ((size_t)P.tile * P.tile + (size_t)(P.tile / 2) * (P.tile / 2) + 1) * sizeof(float);
+    int rc = ct_launch(c, kCtSlotPyrDown,
+                       [&] { k_ct_pyr_down<<<grid, kCtThreads, lds, c->stream>>>(c->d_color.p, c->d_inten.p, P); });
+    if (rc) return rc;
+    const int npx = P.off[P.levels];
+    return ct_launch(c, kCtSlotPyrGrad, [&] {
+        k_ct_pyr_grad<<<(npx + kCtThreads - 1) / kCtThreads, kCtThreads, 0, c->stream>>>(c->d_inten.p, c->d_dIp.p, B, P);
+    });
+}
+
+// What processFrame does with this frame (Undistort.cc:198-228): the photometric value of a source pixel and
+// ImageAndExposure::exposure_time.  Refuses what the frame cannot be read with.
+int und_frame_mode(const ldso_ct_ctx *c, int bits, float exposure_time, int &mode, float &exposure) {
+    if (!c->und_init) return fail(-1, "ldso_ct_undistort_init not called");
+    if (bits != 8 && bits != 16) return fail(-1, "bits must be 8 or 16");
+    const bool valid = c->und_g_depth > 0;
+    if (!valid || exposure_time <= 0 || c->und_mode == 0)
+        mode = kUndFactor;
+    else
+        mode = c->und_mode == 2 ? kUndLutVignette : kUndLut;
+    if (mode != kUndFactor && bits == 16 && c->und_g_depth != 65536)
+        return fail(-1, "a 16-bit frame indexes 65536 entries of G: g_depth is " + std::to_string(c->und_g_depth));
+    exposure = c->und_use_exposure ? exposure_time : 1.0f;
+    return 0;
+}
+
+// k_ct_undistort from the raw frame at dev_raw into d_color, on the context's stream
+int launch_undistort(ldso_ct_ctx *c, const void *dev_raw, int bits, int mode, float factor) {
+    const int n = c->pyr.w * c->pyr.h, nb = (n + kCtThreads - 1) / kCtThreads;
+    const UndParams U{c->d_und_remap.p, c->d_und_g.p, c->d_und_vinv.p, c->und_w_org, n, mode, factor};
+    float *out = c->d_color.p;
+    if (bits == 8) {
+        const uint8_t *raw = static_cast<const uint8_t *>(dev_raw);
+        if (c->und_pass)
+            k_ct_undistort<uint8_t, true><<<nb, kCtThreads, 0, c->stream>>>(raw, out, U);
+        else
+            k_ct_undistort<uint8_t, false><<<nb, kCtThreads, 0, c->stream>>>(raw, out, U);
+    } else {
+        const uint16_t *raw = static_cast<const uint16_t *>(dev_raw);
+        if (c->und_pass)
+            k_ct_undistort<uint16_t, true><<<nb, kCtThreads, 0, c->stream>>>(raw, out, U);
+        else
+            k_ct_undistort<uint16_t, false><<<nb, kCtThreads, 0, c->stream>>>(raw, out, U);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(-2, std::string("launch k_ct_undistort: ") + hipGetErrorString(e));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -904,22 +964,118 @@ int ldso_ct_set_new_frame(ldso_ct_ctx *c, const float *color, double ab_exposure
     HIP_TRY(hipSetDevice(c->device));
     const PyrParams &P = c->pyr;
     HIP_TRY(hipMemcpyAsync(c->d_color.p, color, (size_t)P.w * P.h * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (b_response)
-        HIP_TRY(hipMemcpyAsync(c->d_B.p, b_response, 256 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    const float *B = b_response ? c->d_B.p : nullptr;
-    const dim3 grid(P.w / P.tile, P.h / P.tile);
-    const size_t lds = ((size_t)P.tile * P.tile + (size_t)(P.tile / 2) * (P.tile / 2) + 1) * sizeof(float);
-    int rc = ct_launch(c, kCtSlotPyrDown,
-                       [&] { k_ct_pyr_down<<<grid, kCtThreads, lds, c->stream>>>(c->d_color.p, c->d_inten.p, P); });
-    if (rc) return rc;
-    const int npx = P.off[P.levels];
-    rc = ct_launch(c, kCtSlotPyrGrad, [&] {
-        k_ct_pyr_grad<<<(npx + kCtThreads - 1) / kCtThreads, kCtThreads, 0, c->stream>>>(c->d_inten.p, c->d_dIp.p, B, P);
-    });
+    const int rc = frame_pyramid(c, b_response);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));  // the caller's buffers may be reused on return
     c->new_exposure = (float)ab_exposure;
     c->have_frame = true;
+    return 0;
+}
+
+int ldso_ct_undistort_init(ldso_ct_ctx *c, const ldso_ct_undistort_desc *d, int32_t *n_outside_out) {
+    if (!c || !d) return fail(-1, "null argument");
+    if (d->w_org < 2 || d->h_org < 2) return fail(-1, "the raw image must be at least 2 x 2");
+    if ((d->remap_x == nullptr) != (d->remap_y == nullptr)) return fail(-1, "remap_x and remap_y come together: one of them is NULL");
+    if (d->photometric_mode < 0 || d->photometric_mode > 2) return fail(-1, "photometric_mode out of range [0, 2]");
+    if (d->g && d->g_depth < 256) return fail(-1, "g_depth must be at least 256");
+    if (d->g && !d->vignette_inv) return fail(-1, "g needs vignette_inv: the photometric calibration is valid with both only");
+    const PyrParams &P = c->pyr;
+    const bool pass = !d->remap_x;
+    if (pass && (d->w_org != P.w || d->h_org != P.h))
+        return fail(-1, "passthrough needs a raw image of the context's size " + std::to_string(P.w) + "x" + std::to_string(P.h));
+    if ((int64_t)d->w_org * d->h_org > INT32_MAX / 2) return fail(-1, "the raw image is too large");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // no launch still reads the tables this call replaces
+    c->und_init = false;
+    const size_t n = (size_t)P.w * P.h, n_org = (size_t)d->w_org * d->h_org;
+    int rc, outside = 0;
+    if (!pass) {
+        // the footprint rule (include/ldso_ct.h): what the kernel would read outside the source becomes -1
+        std::vector<float2> m(n);
+        for (size_t i = 0; i < n; i++) {
+            const float xx = d->remap_x[i], yy = d->remap_y[i];
+            m[i] = make_float2(xx, yy);
+            if (xx < 0) continue;  // the reference's own mark: its pixel is 0
+            bool inside = std::isfinite(xx) && std::isfinite(yy) && xx < (float)d->w_org && yy > -1.0f && yy < (float)d->h_org;
+            if (inside) {
+                const int xxi = (int)xx, yyi = (int)yy;
+                inside = xxi + 1 <= d->w_org - 1 && yyi >= 0 && yyi + 1 <= d->h_org - 1;
+            }
+            if (!inside) {
+                m[i] = make_float2(-1.0f, -1.0f);
+                outside++;
+            }
+        }
+        if ((rc = c->d_und_remap.ensure(n))) return rc;
+        HIP_TRY(hipMemcpy(c->d_und_remap.p, m.data(), n * sizeof(float2), hipMemcpyHostToDevice));
+    }
+    if (d->g) {
+        if ((rc = c->d_und_g.ensure((size_t)d->g_depth)) || (rc = c->d_und_vinv.ensure(n_org))) return rc;
+        HIP_TRY(hipMemcpy(c->d_und_g.p, d->g, (size_t)d->g_depth * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_und_vinv.p, d->vignette_inv, n_org * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if ((rc = c->h_und_raw.ensure(n_org * 2)) || (rc = c->d_und_raw.ensure(n_org * 2))) return rc;
+    if ((rc = c->und_ev_prod.ensure(hipEventDisableTiming)) || (rc = c->und_ev_cons.ensure(hipEventDisableTiming))) return rc;
+    c->und_pass = pass;
+    c->und_w_org = d->w_org;
+    c->und_h_org = d->h_org;
+    c->und_g_depth = d->g ? d->g_depth : 0;
+    c->und_mode = d->photometric_mode;
+    c->und_use_exposure = d->use_exposure != 0;
+    c->und_init = true;
+    if (n_outside_out) *n_outside_out = outside;
+    return 0;
+}
+
+int ldso_ct_set_new_frame_raw(ldso_ct_ctx *c, const void *raw, int32_t bits, float exposure_time, float factor,
+                              const float *b_response, float *exposure_out) {
+    if (!c || !raw) return fail(-1, "null argument");
+    int mode;
+    float exposure;
+    int rc = und_frame_mode(c, bits, exposure_time, mode, exposure);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // every use of the pinned frame ends behind a synchronisation, so it is free here
+    const size_t bytes = (size_t)c->und_w_org * c->und_h_org * (bits / 8);
+    std::memcpy(c->h_und_raw.p, raw, bytes);
+    HIP_TRY(hipMemcpyAsync(c->d_und_raw.p, c->h_und_raw.p, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = launch_undistort(c, c->d_und_raw.p, bits, mode, factor)) || (rc = frame_pyramid(c, b_response))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->new_exposure = exposure;
+    c->have_frame = true;
+    if (exposure_out) *exposure_out = exposure;
+    return 0;
+}
+
+int ldso_ct_set_new_frame_raw_device(ldso_ct_ctx *c, const void *dev_raw, int32_t bits, float exposure_time, float factor,
+                                     const float *b_response, void *producer_stream, float *exposure_out) {
+    if (!c || !dev_raw) return fail(-1, "null argument");
+    int mode;
+    float exposure;
+    int rc = und_frame_mode(c, bits, exposure_time, mode, exposure);
+    if (rc) return rc;
+    if (bits == 16 && (reinterpret_cast<uintptr_t>(dev_raw) & 1)) return fail(-1, "a 16-bit device source must be 2-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t prod = static_cast<hipStream_t>(producer_stream);
+    HIP_TRY(hipEventRecord(c->und_ev_prod.e, prod));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->und_ev_prod.e, 0));
+    if ((rc = launch_undistort(c, dev_raw, bits, mode, factor))) return rc;
+    // the producer may overwrite its buffer once the one reader of it has run
+    HIP_TRY(hipEventRecord(c->und_ev_cons.e, c->stream));
+    HIP_TRY(hipStreamWaitEvent(prod, c->und_ev_cons.e, 0));
+    if ((rc = frame_pyramid(c, b_response))) return rc;
+    c->new_exposure = exposure;
+    c->have_frame = true;
+    if (exposure_out) *exposure_out = exposure;
+    return 0;
+}
+
+int ldso_ct_get_undistorted(ldso_ct_ctx *c, float *image) {
+    if (!c || !image) return fail(-1, "null argument");
+    if (!c->have_frame) return fail(-1, "ldso_ct_set_new_frame not called");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(image, c->d_color.p, (size_t)c->pyr.w * c->pyr.h * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
 

@@ -5,6 +5,12 @@ Mirrors the reference class (src/frontend/CoarseTracker.cc) for the parts that r
     CoarseTracker(w, h)                   -> CoarseTracker(width, height)
     makeK(HCalib)                         -> make_k(calib)                     CoarseTracker.cc:312-339
     newFrame->makeImages(color, HCalib)   -> set_new_frame(color, exposure)    FrameHessian.cc:59-115
+    undistorter->undistort(raw, exposure) and makeImages of its image
+                                          -> undistort_init(...) once, then
+                                             set_new_frame_raw(raw, exposure)  Undistort.cc:190-230, 398-453
+                                             undistorted() reads the image back
+    Undistort's constructor (the tables)  -> make_remap(...), make_photometric(...)
+                                                                               Undistort.cc:86-154, 558-1125
     setCoarseTrackingRef's pc_* outputs   -> set_reference(levels, ...)        CoarseTracker.cc:357-538
     makeCoarseDepthL0 on the device       -> make_reference(center, hdi, ...)  CoarseTracker.cc:357-538
                                              make_reference_from(ba_ctx, win)  FullSystem.cc:613-621
@@ -77,6 +83,42 @@ def lm_step(H, b, lam: float, ref_to_new, aff_ab, **params):
     return inc, To, abo
 
 
+def make_remap(model: str, pars, w_org: int, h_org: int, w: int, h: int, out="crop"):
+    """The remap tables of the reference's Undistort constructor on the host (ldso_ct_undistort_make_remap).
+    model: one of _lib.UNDISTORT_MODELS; pars: the calibration's first line (5 or 8 numbers); out: "crop",
+    "none" or the third line's (fx, fy, cx, cy) relative to the output size.
+    Returns (K {fx, fy, cx, cy} float64, remap_x [h*w], remap_y [h*w], passthrough)."""
+    p = np.zeros(8, np.float64)
+    pars = np.asarray(pars, np.float64).reshape(-1)
+    p[:pars.size] = pars
+    if isinstance(out, str):
+        mode, oc = L.UNDISTORT_OUT.index(out), None
+    else:
+        mode, oc = L.UNDISTORT_OUT.index("calib"), _f32(out).reshape(-1)[:4].copy()
+    K = np.zeros(4, np.float64)
+    rx, ry = np.zeros(int(w) * int(h), np.float32), np.zeros(int(w) * int(h), np.float32)
+    passthrough = C.c_int32()
+    L.check(L.lib().ldso_ct_undistort_make_remap(L.UNDISTORT_MODELS.index(model), L.ptr(p, L.f64p), int(w_org), int(h_org),
+                                                 int(w), int(h), mode, L.ptr(oc, L.f32p), L.ptr(K, L.f64p),
+                                                 L.ptr(rx, L.f32p), L.ptr(ry, L.f32p), C.byref(passthrough)))
+    return K, rx, ry, bool(passthrough.value)
+
+
+def make_photometric(g_raw, vignette, photometric_mode: int = 2):
+    """G and vignetteMapInv of the reference's PhotometricUndistorter on the host
+    (ldso_ct_undistort_make_photometric) from the photometric text's first line g_raw and the vignette
+    image's pixels (uint8 or uint16) -> (g [g_depth], vignette_inv, shaped as vignette)."""
+    g_raw = _f32(g_raw).reshape(-1)
+    v = np.ascontiguousarray(vignette)
+    assert v.dtype in (np.uint8, np.uint16), "vignette images are uint8 or uint16"
+    g = np.zeros(g_raw.size, np.float32)
+    vi = np.zeros(v.shape, np.float32)
+    L.check(L.lib().ldso_ct_undistort_make_photometric(L.ptr(g_raw, L.f32p), int(g_raw.size), v.ctypes.data,
+                                                       8 * v.itemsize, int(v.size), int(photometric_mode),
+                                                       L.ptr(g, L.f32p), L.ptr(vi, L.f32p)))
+    return g, vi
+
+
 class CoarseTracker:
     def __init__(self, width: int, height: int, device: int = 0):
         lib = L.lib()
@@ -109,6 +151,66 @@ class CoarseTracker:
         B = None if b_response is None else _f32(b_response)
         assert B is None or B.size == 256
         L.check(L.lib().ldso_ct_set_new_frame(self._h, L.ptr(color, L.f32p), float(ab_exposure), L.ptr(B, L.f32p)))
+
+    # ---- frame ingestion from the raw image (Undistort::undistort, PhotometricUndistorter::processFrame) ----
+    def undistort_init(self, w_org: int, h_org: int, remap=None, g=None, vignette_inv=None,
+                       photometric_mode: int = 2, use_exposure: bool = True) -> int:
+        """The undistorter's tables, once (ldso_ct_undistort_init).  remap: (remap_x, remap_y), each
+        [height*width] at the tracker's size (make_remap's), or None for passthrough; g, vignette_inv:
+        make_photometric's tables, or None for no photometric calibration.  Returns how many entries the
+        footprint rule (include/ldso_ct.h) stored as -1."""
+        n = self.width * self.height
+        rx = ry = None
+        if remap is not None:
+            rx, ry = (None if a is None else _f32(a).reshape(-1) for a in remap)
+            assert all(a is None or a.size == n for a in (rx, ry)), "remap tables are [height*width]"
+        G = None if g is None else _f32(g).reshape(-1)
+        vi = None if vignette_inv is None else _f32(vignette_inv).reshape(-1)
+        assert vi is None or vi.size == int(w_org) * int(h_org), "vignette_inv is [h_org*w_org]"
+        d = L.LdsoCtUndistortDesc(int(w_org), int(h_org), L.ptr(rx, L.f32p), L.ptr(ry, L.f32p), L.ptr(G, L.f32p),
+                                  0 if G is None else int(G.size), L.ptr(vi, L.f32p), int(photometric_mode),
+                                  int(bool(use_exposure)))
+        outside = C.c_int32()
+        L.check(L.lib().ldso_ct_undistort_init(self._h, C.byref(d), C.byref(outside)))
+        self._raw_n = int(w_org) * int(h_org)
+        return int(outside.value)
+
+    def set_new_frame_raw(self, raw, exposure: float = 1.0, factor: float = 1.0, b_response=None, stream=None) -> float:
+        """Undistort::undistort of a raw frame [h_org*w_org] and makeImages of its image.  raw: a NumPy uint8 /
+        uint16 array, or a torch tensor of those types on the GPU, read there with no host synchronisation
+        (ldso_ct_set_new_frame_raw_device; stream: the torch stream or raw hipStream_t that produced it,
+        None = torch's current stream; the tensor must stay alive until the stream work has run).  Returns
+        ImageAndExposure::exposure_time."""
+        B = None if b_response is None else _f32(b_response)
+        assert B is None or B.size == 256
+        out = C.c_float()
+        lib = L.lib()
+        if isinstance(raw, np.ndarray):
+            assert raw.dtype in (np.uint8, np.uint16), "raw frames are uint8 or uint16"
+            a = np.ascontiguousarray(raw).reshape(-1)
+            assert a.size == getattr(self, "_raw_n", a.size), "raw is [h_org*w_org]"
+            L.check(lib.ldso_ct_set_new_frame_raw(self._h, a.ctypes.data, 8 * a.itemsize, float(exposure), float(factor),
+                                                  L.ptr(B, L.f32p), C.byref(out)))
+            return float(out.value)
+        import torch
+
+        assert isinstance(raw, torch.Tensor) and raw.is_cuda and raw.is_contiguous(), \
+            "raw frames are NumPy arrays or contiguous CUDA tensors"
+        assert raw.dtype in (torch.uint8, torch.uint16), "raw frames are uint8 or uint16"
+        assert raw.numel() == getattr(self, "_raw_n", raw.numel()), "raw is [h_org*w_org]"
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        sp = getattr(stream, "cuda_stream", stream)
+        L.check(lib.ldso_ct_set_new_frame_raw_device(self._h, C.c_void_p(raw.data_ptr()), 8 * raw.element_size(),
+                                                     float(exposure), float(factor), L.ptr(B, L.f32p),
+                                                     C.c_void_p(int(sp or 0)), C.byref(out)))
+        return float(out.value)
+
+    def undistorted(self) -> np.ndarray:
+        """The new frame's level-0 image [height, width] (ImageAndExposure::image), read back."""
+        img = np.zeros((self.height, self.width), np.float32)
+        L.check(L.lib().ldso_ct_get_undistorted(self._h, L.ptr(img, L.f32p)))
+        return img
 
     def frame_level(self, lvl: int):
         wl, hl = self.width >> lvl, self.height >> lvl
