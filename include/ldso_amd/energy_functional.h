@@ -40,6 +40,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../ldso_ba.h"
@@ -248,6 +249,31 @@ public:
     // silently, as ldso_ba_load falls back.
     void setResidentFrames(bool on);
     bool residentFrames() const { return resident_; }
+    // Incremental edits (default off; needs resident frames): a structural change turns the loaded
+    // window into the new one with ldso_ba_edit_window -- the points and residuals that survive keep
+    // their device state where it lies, only the new ones and the index arrays go up -- instead of
+    // rebuilding it with ldso_ba_load_frames.  What the host changed on a surviving entry since the
+    // last upload follows as it does without a structural change (ldso_ba_update_points /
+    // _update_residuals).  An edit the library refuses falls back to the reload.
+    // With the switch on a structural change no longer reads the residuals back first: the loaded
+    // window stays on the device until the edit, so the read-back waits for a reader (a residual
+    // method, resetOOB, marginalizePointsF) and, if none comes, never happens -- the surviving
+    // residuals' state goes from the old window into the new one on the device.  Their objects'
+    // fields are then brought up to date on demand as between two passes; the results of the pass
+    // before the edit (state_NewState, centerProjectedTo, JpJdF, the points' HdiF) are not kept on
+    // the device across an edit, as they are not across a load.  The first structural change after
+    // the switch is turned on is a reload.
+    void setIncrementalEdits(bool on) {
+        if (!on) residualTouched();  // a deferred read-back happens now, while the loaded mirror is tracked
+        incremental_ = on;
+    }
+    // Host clock of the structural uploads so far, cumulative ms: [0] their number, [1] residual /
+    // point read-backs (syncResiduals), [2] the graph walk and the mirror's arrays, [3] the frame
+    // terms, [4] ldso_ba_edit_window or the reload, [5] the follow-up updates of points / residuals.
+    const double *uploadSplit() const { return split_; }
+    bool incrementalEdits() const { return incremental_; }
+    long editsApplied() const { return editsApplied_; }
+    long editsFallenBack() const { return editsFallenBack_; }
     void dropResidual(shared_ptr<PointFrameResidual> r);
     void marginalizeFrame(shared_ptr<FrameHessian> fh);
     void removePoint(shared_ptr<PointHessian> ph);
@@ -349,6 +375,16 @@ public:
     void residualTouched() {
         if (resSync_ == ResSync::DeviceNewer) syncResiduals();
     }
+    // a structural change begins: as residualTouched, unless an edit can carry the device's state
+    // (incremental edits, the loaded window tracked): then the read-back is deferred (see
+    // setIncrementalEdits)
+    void structuralTouch() {
+        if (incremental_ && mirrorTracked_ && resSync_ == ResSync::DeviceNewer) {
+            deferred_ = true;
+            return;
+        }
+        residualTouched();
+    }
     void residualEdited() { resSync_ = ResSync::HostNewer; }
     double linearizeResidual(PointFrameResidual &r);
 
@@ -415,6 +451,20 @@ private:
     int width_ = 0, height_ = 0;
     // frame store: resident_ selects the path; the store's size as reserved and the frameIDs in it
     bool resident_ = true;
+    // incremental edits: the frameIDs of the window as loaded by id (empty: none is), the loaded
+    // mirror's points by address (insertPoint takes an address out: it may be a new object's)
+    bool incremental_ = false;
+    bool mirrorTracked_ = false;  // the loaded mirror was built with the switch on (mirrorPoint_ is its)
+    bool deferred_ = false;       // structural changes are pending and the device is still newer
+    long lostResultsAt_ = -1;     // passes_ at an edit that carried state the host never read
+    double split_[6] = {0, 0, 0, 0, 0, 0};
+    void forgetResidual(const PointFrameResidual *r) {  // r leaves the loaded mirror
+        const int m = r->mirrorIdx;
+        if (incremental_ && m >= 0 && (size_t)m < resPtr_.size() && resPtr_[m] == r) resPtr_[m] = nullptr;
+    }
+    long editsApplied_ = 0, editsFallenBack_ = 0;
+    std::vector<int> loadedIds_;
+    std::unordered_map<const PointHessian *, int> mirrorPoint_;
     int storeW_ = 0, storeH_ = 0;
     std::vector<int> storeIds_;
     ResSync resSync_ = ResSync::Synced;

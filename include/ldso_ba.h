@@ -286,9 +286,71 @@ int ldso_ba_frame_get(ldso_ba_ctx *ctx, int64_t frame_id, float *intensity, floa
 int ldso_ba_load_frames(ldso_ba_ctx *ctx, int32_t n_windows, const ldso_ba_window *windows,
                         const int64_t *frame_ids, int32_t shard_rank, int32_t shard_count);
 /* out[4] = image bytes host -> device, image bytes device -> device, image buffer (re)allocations
- * (window images, store, staging), frames ingested -- cumulative per context, counted at the
- * library's own call sites (ldso_ba_load counts too). */
+ * (window images, store, staging) plus every buffer ldso_ba_edit_window had to grow, frames ingested
+ * -- cumulative per context, counted at the library's own call sites (ldso_ba_load counts too). */
 int ldso_ba_transfer_stats(ldso_ba_ctx *ctx, int64_t out[4]);
+
+/* ---- editing a loaded window in place --------------------------------------------------
+ * The keyframe cycle's structural changes (residuals dropped, points removed, frames removed with the
+ * index shift of makeIDX, frames appended, new residuals on carried points, new points with their
+ * residuals anywhere in the point order) without reloading what the device already holds: the
+ * context's window `win` becomes the window `after` describes.
+ *   after      the structure in full, as for a load (n_*, sizes, calib, point_host, point_res_begin,
+ *              res_target, point_rank), and the frame-level arrays ldso_ba_update takes (precalc,
+ *              adjoints, priors, c_delta, frame_energy_th).  point_data, res_state, res_energy and
+ *              res_flags are read ONLY at entries whose *_src is -1 (they may be NULL if there are
+ *              none); after->dI is ignored.
+ *   frame_ids  [after->n_frames], as ldso_ba_load_frames
+ *   frame_src  [after->n_frames]: the frame's index in the loaded window, -1 = a new frame
+ *   point_src  [after->n_points]: the point's index in the loaded window (caller order), -1 = new
+ *   res_src    [after->n_residuals]: the residual's index in the loaded window (caller order), -1 = new
+ * A carried point keeps its whole device record (the inverse depths the device loop stepped
+ * included); a carried residual keeps state_state, state_energy, state_NewEnergy and its flags as the
+ * device holds them.
+ * Contract: after a successful edit every sequence of library calls gives, bit for bit, what it gives
+ * after ldso_ba_load_frames(after') on a context with the same settings and tuning keys, after' being
+ * `after` with the carried entries filled in from the device (ldso_ba_get_residuals' state /
+ * state_energy / flags, the point record, and ldso_ba_update_residuals where state_NewEnergy differs
+ * from state_energy).  The device arrays are the ones build_layout gives for `after`; results of the
+ * last pass are undefined until the next one, as after a load.
+ * The call runs on the context stream without a host synchronisation and allocates only when a
+ * buffer's capacity is exceeded (capacities then grow by half, so a steady cycle allocates nothing).
+ * Refused (< 0 with a message, before anything of the context changes): a context that holds more
+ * or fewer than one window; a window not loaded with ldso_ba_load_frames; a sharded context or one
+ * with a communicator; a marginalisation context; LDSO_BA_TUNE_ITEM_ORDER 2 (its order depends on a
+ * float sort of the point records); an old index used twice or out of range; a carried residual whose
+ * point is not the image of its old point; a carried point or residual whose host or target is not
+ * frame_src's image of the old one, or is a removed frame; a frame id that is not resident
+ * (LDSO_BA_ERR_FRAME_STORE); anything ldso_ba_validate_window rejects in `after`.  A failed device
+ * allocation (-3) is not a refusal: as after a failed load, the context must be loaded again. */
+typedef struct ldso_ba_edit {
+    const ldso_ba_window *after;
+    const int64_t *frame_ids;
+    const int32_t *frame_src;
+    const int32_t *point_src;
+    const int32_t *res_src;
+} ldso_ba_edit;
+int ldso_ba_edit_window(ldso_ba_ctx *ctx, int32_t win, const ldso_ba_edit *e);
+/* Where the edits' time went, cumulative per context: out[6] = edits applied; host clock (ms) of the
+ * planner, of the rest of the call (growth, staging copies, launches, image copies) and of the whole
+ * call; and, for edits made while kernel timing is on (ldso_ba_set_kernel_timing; three HIP events
+ * per edit, read here or at the next edit with one event synchronisation), the device time (ms) of
+ * the staging launches and of k_edit_gather. */
+int ldso_ba_edit_stats(ldso_ba_ctx *ctx, double out[6]);
+/* The edit's host planner alone, no GPU needed (tests): `before` is laid out as ldso_ba_load_frames
+ * lays it out, the edit is planned against it as ldso_ba_edit_window plans it (item_order, top_chunk:
+ * the tuning keys; e->frame_ids is not read), and the plan is returned.  Outputs (any may be NULL):
+ *   res_gather [after R], point_gather [after P]   per device-order entry of the edited window: its
+ *              old device position (>= 0), or ~rank (< 0), rank counting the new entries in caller order
+ *   before_res_order [before R], before_point_order [before P], after_res_order [after R],
+ *   after_point_order [after P]                    device position -> caller index
+ *   n_mismatch  the number of index arrays (work items, record slots, target lists, counts, bases of
+ *              the descriptor, device orders) in which the plan's layout differs from the layout of
+ *              `after` itself, which for this output must carry every array a load needs. */
+int ldso_ba_edit_plan_check(const ldso_ba_window *before, const ldso_ba_edit *e, int32_t item_order, int32_t top_chunk,
+                            int32_t *res_gather, int32_t *point_gather, int32_t *before_res_order,
+                            int32_t *before_point_order, int32_t *after_res_order, int32_t *after_point_order,
+                            int32_t *n_mismatch);
 
 /* Refresh per-iteration state of window `win` after doStepFromBackup / setPrecalcValues:
  * precalc, adjoints, priors, cDeltaF, frame_energy_th and point_data (all 24 floats per point;
@@ -397,6 +459,11 @@ int ldso_ba_get_residuals(ldso_ba_ctx *ctx, int32_t win, int8_t *new_state, int8
  * Points with no active residual report HdiF = bdSumF = idepth_hessian = 0. */
 int ldso_ba_get_points(ldso_ba_ctx *ctx, int32_t win, float *HdiF, float *bdSumF,
                        float *idepth_hessian, float *Hdd_acc, float *bd_acc, float *Hcd_acc);
+/* The point records as the device holds them now, [P][LDSO_BA_POINT_STRIDE] in caller order
+ * (synchronising; test / debug and the read-back of ldso_ba_edit_window's contract): what was
+ * loaded or updated, with the values ldso_ba_optimize stepped.  A sharded window writes its own
+ * points only. */
+int ldso_ba_get_point_data(ldso_ba_ctx *ctx, int32_t win, float *point_data);
 int ldso_ba_get_frame_energy_th(ldso_ba_ctx *ctx, int32_t win, float *th);
 
 /* solveSystemF on the stitched system of the last pass (get_system + ldso_ba_solve_system):

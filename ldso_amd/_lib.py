@@ -107,6 +107,12 @@ class LdsoBaWindow(C.Structure):
     ]
 
 
+class LdsoBaEdit(C.Structure):
+    """ldso_ba_edit (include/ldso_ba.h)"""
+    _fields_ = [("after", C.POINTER(LdsoBaWindow)), ("frame_ids", i64p), ("frame_src", i32p), ("point_src", i32p),
+                ("res_src", i32p)]
+
+
 def source_sha256() -> str | None:
     """sha256 over the sources libldso_ba.so is built from (ldso_amd/csrc, include/ldso_ba.h,
     include/ldso_ct.h): the identity of a build that survives a rebuild on another machine (the .so
@@ -217,6 +223,12 @@ ABI = [
     ("ldso_ba_frame_get", C.c_int, [C.c_void_p, C.c_int64, f32p, f32p]),
     ("ldso_ba_load_frames", C.c_int, [C.c_void_p, C.c_int32, C.POINTER(LdsoBaWindow), i64p, C.c_int32, C.c_int32]),
     ("ldso_ba_transfer_stats", C.c_int, [C.c_void_p, i64p]),
+    # editing a loaded window in place
+    ("ldso_ba_edit_window", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    ("ldso_ba_get_point_data", C.c_int, [C.c_void_p, C.c_int32, f32p]),
+    ("ldso_ba_edit_stats", C.c_int, [C.c_void_p, f64p]),
+    ("ldso_ba_edit_plan_check", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, i32p, i32p, i32p, i32p, i32p,
+                                          i32p, i32p]),
 ]
 ERR_FRAME_STORE, ERR_GRADIENT_MISMATCH = -4, -5
 

@@ -73,6 +73,26 @@ class BAContext:
             w._keep = []  # host copies are no longer referenced by the device
         return self
 
+    def edit(self, after: Window, frame_ids, frame_src, point_src, res_src, win: int = 0):
+        """ldso_ba_edit_window: window `win` becomes `after`, the carried entries (src >= 0) taken from
+        where the device holds them; after's point_data / res_state / res_energy / res_flags are read at
+        entries whose src is -1 only.  A refused edit raises and leaves the context as it was."""
+        s = after.c_struct(with_images=False)
+        ids = np.ascontiguousarray(np.asarray(frame_ids).reshape(-1), np.int64)
+        src = [np.ascontiguousarray(a, np.int32) for a in (frame_src, point_src, res_src)]
+        assert ids.size == src[0].size == after.n_frames and src[1].size == after.n_points and src[2].size == after.n_residuals
+        e = L.LdsoBaEdit(C.pointer(s), L.ptr(ids, L.i64p), *[L.ptr(a, L.i32p) for a in src])
+        L.check(self._lib.ldso_ba_edit_window(self._h, int(win), C.byref(e)))
+        self.windows[win] = after
+        after._keep = []
+        return self
+
+    def point_data(self, win: int = 0) -> np.ndarray:
+        """ldso_ba_get_point_data: the point records [P][24] as the device holds them, caller order."""
+        out = np.zeros((self.windows[win].n_points, L.POINT_STRIDE), np.float32)
+        L.check(self._lib.ldso_ba_get_point_data(self._h, int(win), L.ptr(out, L.f32p)))
+        return out
+
     # ---- device-resident frame store -----------------------------------------------------
     def frames_reserve(self, capacity: int, width: int, height: int):
         """ldso_ba_frames_reserve: `capacity` image slots in the context's image layout

@@ -6,6 +6,7 @@
 #include "../../include/ldso_ct.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 
 namespace ldso_amd {
@@ -97,6 +98,7 @@ bool read_residuals(ldso_ba_ctx *ctx, const std::vector<PointFrameResidual *> &r
                               rb.data()))
         return false;
     for (size_t k = 0; k < R; k++) {
+        if (!res[k]) continue;  // dropped since the load (a deferred read-back, see structuralTouch)
         PointFrameResidual &r = *res[k];
         r.state_NewState = (ResState)ns[k];
         r.state_state = (ResState)st[k];
@@ -218,7 +220,7 @@ void EnergyFunctional::packFrames(std::vector<ldso_ba_frame_state> &fs) const {
 
 // EnergyFunctional.cc:45-49 (the caller has pushed r into its point's residuals)
 void EnergyFunctional::insertResidual(shared_ptr<PointFrameResidual> r) {
-    residualTouched();  // before any structural change: the mirror's residuals may not outlive it
+    structuralTouch();  // before any structural change: the mirror's residuals may not outlive it
     r->ef = this;
     r->mirrorIdx = -1;
     connectivityMap[conn_key(*r)][0]++;
@@ -320,7 +322,7 @@ void EnergyFunctional::setResidentFrames(bool on) {
 
 void EnergyFunctional::insertFrameImpl(shared_ptr<FrameHessian> fh, shared_ptr<CalibHessian> Hcalib,
                                        const ldso_ct_ctx *tracker) {
-    residualTouched();
+    structuralTouch();
     fh->takeData(&settings_);
     frames.push_back(fh);
     fh->idx = (int)frames.size();
@@ -356,9 +358,10 @@ void EnergyFunctional::insertFrameImpl(shared_ptr<FrameHessian> fh, shared_ptr<C
 }
 
 void EnergyFunctional::insertPoint(shared_ptr<PointHessian> ph) {
-    residualTouched();
+    structuralTouch();
     ph->status = PointStatus::ACTIVE;
     ph->alreadyRemoved = false;
+    mirrorPoint_.erase(ph.get());  // a new point, even at the address of one the mirror held
     registry_.push_back(ph);
     allPoints.push_back(ph);
     nPoints++;
@@ -368,7 +371,7 @@ void EnergyFunctional::insertPoint(shared_ptr<PointHessian> ph) {
 
 // EnergyFunctional.cc:100-107
 void EnergyFunctional::dropResidual(shared_ptr<PointFrameResidual> r) {
-    residualTouched();
+    structuralTouch();
     shared_ptr<PointHessian> p = r->point.lock();
     if (p) {
         auto &v = p->residuals;
@@ -378,6 +381,7 @@ void EnergyFunctional::dropResidual(shared_ptr<PointFrameResidual> r) {
     connectivityMap[conn_key(*r)][0]--;
     nResiduals--;
     if (r->ef == this) r->ef = nullptr;
+    forgetResidual(r.get());
     r->mirrorIdx = -1;
     dirty_ = true;
     epoch_++;
@@ -386,7 +390,7 @@ void EnergyFunctional::dropResidual(shared_ptr<PointFrameResidual> r) {
 // EnergyFunctional.cc:109-191: the dense reorder / prior / Schur step on the host
 // (ldso_ba_marginalize_frame), then the frame leaves the window
 void EnergyFunctional::marginalizeFrame(shared_ptr<FrameHessian> fh) {
-    residualTouched();
+    structuralTouch();
     const int no = 8 * nFrames + CPARS, nn = no - 8;
     MatXX Ho(nn, nn);
     VecX bo(nn);
@@ -414,12 +418,20 @@ void EnergyFunctional::marginalizeFrame(shared_ptr<FrameHessian> fh) {
 
 // EnergyFunctional.cc:193-203
 void EnergyFunctional::removePoint(shared_ptr<PointHessian> ph) {
-    residualTouched();
+    structuralTouch();
     for (const shared_ptr<PointFrameResidual> &r : ph->residuals) {
         connectivityMap[conn_key(*r)][0]--;
         nResiduals--;
         if (r->ef == this) r->ef = nullptr;
+        forgetResidual(r.get());
         r->mirrorIdx = -1;
+    }
+    if (incremental_) {
+        const auto it = mirrorPoint_.find(ph.get());
+        if (it != mirrorPoint_.end()) {
+            if ((size_t)it->second < ptPtr_.size() && ptPtr_[it->second] == ph.get()) ptPtr_[it->second] = nullptr;
+            mirrorPoint_.erase(it);
+        }
     }
     ph->residuals.clear();
     if (!ph->alreadyRemoved) nPoints--;
@@ -494,7 +506,7 @@ void EnergyFunctional::marginalizePointsF() {
 
 // EnergyFunctional.cc:264-278
 void EnergyFunctional::dropPointsF() {
-    residualTouched();
+    structuralTouch();
     for (const shared_ptr<PointHessian> &p : registry_)
         if ((p->status == PointStatus::OUTLIER || p->status == PointStatus::OUT) && !p->alreadyRemoved) removePoint(p);
     makeIDX();
@@ -503,7 +515,7 @@ void EnergyFunctional::dropPointsF() {
 // EnergyFunctional.cc:500-521: frame indices; the active, not removed points in host-frame order
 // (the reference walks its frames' features; registry_ is that list)
 void EnergyFunctional::makeIDX() {
-    residualTouched();
+    structuralTouch();
     epoch_++;
     for (size_t i = 0; i < frames.size(); i++) frames[i]->idx = (int)i;
     std::vector<shared_ptr<PointHessian>> keep, live;
@@ -687,21 +699,67 @@ bool EnergyFunctional::upload() {
         return true;
     }
     // structural change: rebuild the mirror (the only place the weak_ptr graph is walked)
-    residualTouched();
+    using SplitClock = std::chrono::steady_clock;
+    auto ms_since = [](SplitClock::time_point t) { return std::chrono::duration<double, std::milli>(SplitClock::now() - t).count(); };
+    SplitClock::time_point t_part = SplitClock::now();
+    // incremental edits: an edit can be tried if the loaded window's entries were tracked
+    bool tryEdit = incremental_ && resident_ && mirrorTracked_ && !loadedIds_.empty();
+    if (deferred_ && !tryEdit) syncResiduals();  // the reload below sends the host's values: make them current
     if (!uploadFrameTerms()) return false;
+    split_[3] += ms_since(t_part);
+    t_part = SplitClock::now();
+    // the loaded mirror's entries, compared by address and never dereferenced (dropped ones are null)
+    std::vector<PointFrameResidual *> oldRes;
+    std::vector<PointHessian *> oldPt;
+    std::vector<float> oldVals;
+    if (tryEdit) {
+        oldRes = resPtr_;
+        oldPt = ptPtr_;
+        oldVals = pointVals_;
+    }
     ptPtr_.clear();
     for (const shared_ptr<PointHessian> &p : allPoints) ptPtr_.push_back(p.get());
     PointPack pk;
     pk.build(ptPtr_);
-    pointHost_ = pk.host;
-    pointRank_ = pk.rank;
-    pointRanked_ = pk.ranked;
-    pointData_ = pk.data;
-    resBegin_ = pk.begin;
-    resTarget_ = pk.target;
-    resState_ = pk.state;
-    resEnergy_ = pk.energy;
-    resFlags_ = pk.flags;
+    // where every entry of the new mirror lies in the loaded one (-1: new).  A residual keeps its
+    // mirrorIdx until it is inserted or dropped; a point is found by address.
+    std::vector<int32_t> pointSrc, resSrc;
+    if (tryEdit) {
+        pointSrc.assign(ptPtr_.size(), -1);
+        resSrc.assign(pk.res.size(), -1);
+        for (size_t q = 0; q < ptPtr_.size(); q++) {
+            const auto it = mirrorPoint_.find(ptPtr_[q]);
+            if (it != mirrorPoint_.end()) pointSrc[q] = it->second;
+        }
+        bool new_ne_differs = false;
+        for (size_t k = 0; k < pk.res.size(); k++) {
+            const int m = pk.res[k]->mirrorIdx;
+            if (m >= 0 && (size_t)m < oldRes.size() && oldRes[m] == pk.res[k]) resSrc[k] = m;
+            else new_ne_differs = new_ne_differs || (float)pk.res[k]->state_NewEnergy != pk.energy[k];
+        }
+        // a deferred read-back stays deferred through the edit only if the new residuals need no
+        // upload of their own afterwards (state_NewEnergy is loaded equal to state_energy)
+        if (deferred_ && new_ne_differs) {
+            resPtr_.swap(oldRes);
+            ptPtr_.swap(oldPt);
+            syncResiduals();  // reads the loaded window into the loaded mirror's objects
+            resPtr_.swap(oldRes);
+            ptPtr_.swap(oldPt);
+            pk.build(ptPtr_);
+        }
+    }
+    auto adopt_pack = [&]() {
+        pointHost_ = pk.host;
+        pointRank_ = pk.rank;
+        pointRanked_ = pk.ranked;
+        pointData_ = pk.data;
+        resBegin_ = pk.begin;
+        resTarget_ = pk.target;
+        resState_ = pk.state;
+        resEnergy_ = pk.energy;
+        resFlags_ = pk.flags;
+    };
+    adopt_pack();
     resPtr_ = pk.res;
     nResiduals = (int)resPtr_.size();
     resPoint_.resize(resPtr_.size());
@@ -764,17 +822,93 @@ bool EnergyFunctional::upload() {
     w.res_energy = resEnergy_.data();
     w.res_flags = resFlags_.data();
     w.point_rank = pointRanked_ ? pointRank_.data() : nullptr;
+    mirrorTracked_ = incremental_ && resident_;
+    if (mirrorTracked_) {
+        mirrorPoint_.clear();
+        for (size_t q = 0; q < ptPtr_.size(); q++) mirrorPoint_[ptPtr_[q]] = (int)q;
+    }
+    split_[0] += 1;
+    split_[2] += ms_since(t_part);
+    t_part = SplitClock::now();
+    if (tryEdit && resident_) {
+        std::vector<int32_t> frameSrc(N, -1);
+        for (int f = 0; f < N; f++) {
+            const auto it = std::find(loadedIds_.begin(), loadedIds_.end(), frames[f]->frameID);
+            if (it != loadedIds_.end()) frameSrc[f] = (int32_t)(it - loadedIds_.begin());
+        }
+        const ldso_ba_edit ed = {&w, ids.data(), frameSrc.data(), pointSrc.data(), resSrc.data()};
+        if (ldso_ba_edit_window(ctx_, 0, &ed) == 0) {
+            split_[4] += ms_since(t_part);
+            t_part = SplitClock::now();
+            editsApplied_++;
+            loadedIds_.assign(ids.begin(), ids.end());
+            // the device holds, on a surviving point, the values it held before: the branch above
+            // sends the points' values if the host's differ
+            for (size_t q = 0; q < ptPtr_.size(); q++)
+                if (pointSrc[q] >= 0 && (size_t)4 * pointSrc[q] + 3 < oldVals.size())
+                    std::memcpy(&pointVals_[4 * q], &oldVals[4 * (size_t)pointSrc[q]], 4 * sizeof(float));
+            if (deferred_) {
+                // the surviving residuals' state never came to the host and went into the new window
+                // on the device; the last pass's results are gone, as after a load
+                deferred_ = false;
+                lostResultsAt_ = passes_;
+                outStatePass_ = outCenterPass_ = -1;  // cached in the loaded mirror's order
+                outState_.assign(resPtr_.size(), 0);
+            } else {
+                // ... and on a surviving residual the state the host read back (or edited since:
+                // HostNewer, sent by the branch above)
+                bool ne_differs = false;
+                for (size_t k = 0; k < resPtr_.size() && !ne_differs; k++)
+                    ne_differs = (float)resPtr_[k]->state_NewEnergy != resEnergy_[k];
+                if (ne_differs) resSync_ = ResSync::HostNewer;
+            }
+            dirty_ = false;
+            const bool done = upload();
+            split_[5] += ms_since(t_part);
+            return done;
+        }
+        editsFallenBack_++;  // refused (ldso_ba_last_error says why): the reload below
+        if (deferred_) {  // the loaded window is untouched: read it into the loaded mirror's objects first
+            std::vector<PointFrameResidual *> newRes = resPtr_;
+            std::vector<PointHessian *> newPt = ptPtr_;
+            resPtr_ = oldRes;
+            ptPtr_ = oldPt;
+            syncResiduals();
+            resPtr_ = newRes;
+            ptPtr_ = newPt;
+            pk.build(ptPtr_);
+            adopt_pack();
+            w.point_host = pointHost_.data();
+            w.point_data = pointData_.data();
+            w.point_res_begin = resBegin_.data();
+            w.res_target = resTarget_.data();
+            w.res_state = resState_.data();
+            w.res_energy = resEnergy_.data();
+            w.res_flags = resFlags_.data();
+            w.point_rank = pointRanked_ ? pointRank_.data() : nullptr;
+        }
+    }
+    loadedIds_.clear();
+    deferred_ = false;
+    lostResultsAt_ = -1;
     if (resident_ ? ldso_ba_load_frames(ctx_, 1, &w, ids.data(), 0, 1) : ldso_ba_load(ctx_, 1, &w, 0, 1)) {
         fail(resident_ ? "ldso_ba_load_frames" : "ldso_ba_load");
         return false;
     }
+    if (resident_) loadedIds_.assign(ids.begin(), ids.end());
     // the device's state_NewEnergy starts as state_energy (ldso_ba_load); the host's may differ
     bool ne_differs = false;
     for (size_t k = 0; k < resPtr_.size() && !ne_differs; k++)
         ne_differs = (float)resPtr_[k]->state_NewEnergy != resEnergy_[k];
     resSync_ = ne_differs ? ResSync::HostNewer : ResSync::Synced;
     dirty_ = false;
-    if (resSync_ == ResSync::HostNewer) return upload();
+    split_[4] += ms_since(t_part);
+    if (resSync_ == ResSync::HostNewer) {
+        t_part = SplitClock::now();
+        const bool done = upload();
+        split_[5] += ms_since(t_part);
+        return done;
+    }
     return true;
 }
 
@@ -790,28 +924,55 @@ void EnergyFunctional::resetOOB() {
     if (!dirty_ && ctx_) {
         if (ldso_ba_reset_oob(ctx_, 0)) fail("ldso_ba_reset_oob");
         else if (resSync_ == ResSync::DeviceNewer) resSync_ = ResSync::Synced;
+    } else if (incremental_) {
+        resSync_ = ResSync::HostNewer;  // an edit carries the device's residual state: the reset ones follow it
     }
 }
 
 // every per-residual / per-point result of the device's last pass into the objects
 bool EnergyFunctional::readBack(bool points_and_th) {
+    if (lostResultsAt_ == passes_) {
+        // an edit carried the residuals' state past the host and reset the last pass's results, as a
+        // load does: state, energy and flags are what the device still knows
+        const size_t R = resPtr_.size();
+        std::vector<int8_t> st(R);
+        std::vector<float> se(R);
+        std::vector<uint8_t> fl(R);
+        if (R && ldso_ba_get_residuals(ctx_, 0, nullptr, st.data(), se.data(), nullptr, nullptr, fl.data(), nullptr, nullptr)) {
+            fail("ldso_ba_get_residuals");
+            return false;
+        }
+        for (size_t k = 0; k < R; k++) {
+            if (!resPtr_[k]) continue;
+            PointFrameResidual &r = *resPtr_[k];
+            r.state_state = (ResState)st[k];
+            r.state_energy = r.state_NewEnergy = se[k];
+            r.isActiveAndIsGoodNEW = (fl[k] & LDSO_BA_FLAG_ACTIVE) != 0;
+        }
+        resSync_ = ResSync::Synced;
+        return true;
+    }
     if (!read_residuals(ctx_, resPtr_)) {
         fail("ldso_ba_get_residuals");
         return false;
     }
     resSync_ = ResSync::Synced;
     if (!points_and_th) return true;
-    const int P = (int)ptPtr_.size(), N = nFrames;
-    std::vector<float> hdi(P), bds(P), ih(P), th(N);
+    const int P = (int)ptPtr_.size();
+    std::vector<float> hdi(P), bds(P), ih(P);
     if (P && ldso_ba_get_points(ctx_, 0, hdi.data(), bds.data(), ih.data(), nullptr, nullptr, nullptr)) {
         fail("ldso_ba_get_points");
         return false;
     }
     for (int q = 0; q < P; q++) {
+        if (!ptPtr_[q]) continue;  // removed since the load (a deferred read-back)
         ptPtr_[q]->HdiF = hdi[q];
         ptPtr_[q]->bdSumF = bds[q];
         ptPtr_[q]->idepth_hessian = ih[q];
     }
+    if (dirty_) return true;  // the frames may have changed since the load: their thresholds were read with the pass
+    const int N = nFrames;
+    std::vector<float> th(N);
     if (ldso_ba_get_frame_energy_th(ctx_, 0, th.data()) == 0) {
         for (int f = 0; f < N; f++) frames[f]->frameEnergyTH = th[f];
         thUp_ = th;  // the device holds these already
@@ -915,9 +1076,14 @@ bool EnergyFunctional::setCoarseTrackingRef(ldso_ct_ctx *tracker, const ldso_ct_
 }
 
 void EnergyFunctional::syncResiduals() {
-    if (resSync_ != ResSync::DeviceNewer || !ctx_ || dirty_) return;
+    // after a structural change the device's window is no longer the mirror's, unless the read-back
+    // was deferred for an edit (structuralTouch): then the loaded window is still there to read
+    if (resSync_ != ResSync::DeviceNewer || !ctx_ || (dirty_ && !deferred_)) return;
     resSync_ = ResSync::Synced;  // before the reads: the residual setters called below see it synced
+    deferred_ = false;
+    const auto t0 = std::chrono::steady_clock::now();
     readBack(true);
+    split_[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 Vec3 EnergyFunctional::linearizeAll(bool fixLinearization) {

@@ -26,6 +26,13 @@
 //                   once with setResidentFrames(false) (every reload gathers and uploads all images),
 //                   each with its ldso_ba_transfer_stats deltas per cycle; ingest_us: one
 //                   ldso_ba_frame_put_tracker of a 640x480 frame, host clock over a back-to-back run
+//   keyframe_cycle_incremental  only with `ldso_face_bench REPS --incremental`: the resident cycle
+//                   with setIncrementalEdits off and on (the structural round becomes one
+//                   ldso_ba_edit_window), alternated A B A B in this process, each run with its own
+//                   warm-up, the timed cycles of each kind pooled (median, min, max); split: where a
+//                   cycle's structural uploads spend their host time (EnergyFunctional::uploadSplit and
+//                   ldso_ba_edit_stats, ms per cycle); device: a further incremental run with kernel
+//                   timing on, whose HIP events bracket the edit's staging launches and k_edit_gather
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -51,6 +58,7 @@ static double ms_since(Clock::time_point t0) {
 int main(int argc, char **argv) {
     const int N = 7, P = 2000, W = 640, H = 480, n_its = 6;
     const int reps = argc > 1 ? std::atoi(argv[1]) : 10;
+    const bool with_incremental = argc > 2 && std::strcmp(argv[2], "--incremental") == 0;
     const int R = P * (N - 1);
     std::vector<ldso_ba_frame_state> fs(N);
     std::vector<float> dI((size_t)N * W * H * 3), th(N), pd((size_t)P * LDSO_BA_POINT_STRIDE), re(R);
@@ -388,12 +396,25 @@ int main(int argc, char **argv) {
         double med = -1, lo = -1, hi = -1;
         double xfer[4] = {0, 0, 0, 0};
         bool ok = false;
+        std::vector<double> ms;  // every timed cycle
+        long edits = 0, fallen = 0;
+        int cycles = 0;
+        double split[6] = {0, 0, 0, 0, 0, 0};  // EnergyFunctional::uploadSplit over the timed cycles
+        double lib[6] = {0, 0, 0, 0, 0, 0};    // ldso_ba_edit_stats over the timed cycles
     };
-    auto keyframe_cycle = [&](bool resident) {
+    // events: kernel timing on with an empty slot mask, so that only the edit's three events are
+    // recorded (timing also makes ldso_ba_optimize launch directly: such a run's cycle time is not reported)
+    auto keyframe_cycle = [&](bool resident, bool incremental = false, bool events = false) {
         CycleResult out;
         auto e2 = std::make_shared<EnergyFunctional>(0);
         if (!e2->ok()) return out;
         e2->setResidentFrames(resident);
+        e2->setIncrementalEdits(incremental);
+        if (events) {
+            ldso_ba_set_tuning(e2->context(), LDSO_BA_TUNE_TIMING_MASK, 0);
+            ldso_ba_set_kernel_timing(e2->context(), 1);
+        }
+        double split0[6] = {0, 0, 0, 0, 0, 0}, lib0[6] = {0, 0, 0, 0, 0, 0};
         auto make_frame = [&](int f, int id) {
             auto F = std::make_shared<FrameHessian>();
             F->frameID = id;
@@ -436,7 +457,11 @@ int main(int argc, char **argv) {
         std::vector<double> ms;
         int64_t x0[4] = {0, 0, 0, 0}, x1[4] = {0, 0, 0, 0};
         for (int c = 0; c < warm + reps && e2->ok(); c++) {
-            if (c == warm) ldso_ba_transfer_stats(e2->context(), x0);
+            if (c == warm) {
+                ldso_ba_transfer_stats(e2->context(), x0);
+                std::memcpy(split0, e2->uploadSplit(), sizeof(split0));
+                ldso_ba_edit_stats(e2->context(), lib0);
+            }
             auto F = make_frame(N - 1, 100 + c);
             std::vector<shared_ptr<PointFrameResidual>> added;
             auto t1 = Clock::now();
@@ -461,6 +486,15 @@ int main(int argc, char **argv) {
             std::fprintf(stderr, "keyframe_cycle: %s\n", e2->lastError().c_str());
             return out;
         }
+        out.ms = ms;
+        out.cycles = (int)ms.size();
+        ldso_ba_edit_stats(e2->context(), out.lib);
+        for (int i = 0; i < 6; i++) {
+            out.split[i] = e2->uploadSplit()[i] - split0[i];
+            out.lib[i] -= lib0[i];
+        }
+        out.edits = e2->editsApplied();
+        out.fallen = e2->editsFallenBack();
         std::sort(ms.begin(), ms.end());
         out.med = ms[ms.size() / 2];
         out.lo = ms.front();
@@ -470,6 +504,63 @@ int main(int argc, char **argv) {
         return out;
     };
     const CycleResult kc_res = keyframe_cycle(true), kc_leg = keyframe_cycle(false);
+    // --incremental: the resident cycle with and without incremental edits (setIncrementalEdits), the
+    // two alternated in this process (A B A B, each with its own warm-up), their cycles pooled
+    std::string kc_inc_json;
+    if (with_incremental) {
+        auto pool = [](CycleResult a, const CycleResult &b) {
+            a.ok = a.ok && b.ok;
+            a.ms.insert(a.ms.end(), b.ms.begin(), b.ms.end());
+            if (a.ok) {
+                std::sort(a.ms.begin(), a.ms.end());
+                a.med = a.ms[a.ms.size() / 2];
+                a.lo = a.ms.front();
+                a.hi = a.ms.back();
+            }
+            for (int i = 0; i < 4; i++) a.xfer[i] = 0.5 * (a.xfer[i] + b.xfer[i]);
+            a.edits += b.edits;
+            a.fallen += b.fallen;
+            a.cycles += b.cycles;
+            for (int i = 0; i < 6; i++) {
+                a.split[i] += b.split[i];
+                a.lib[i] += b.lib[i];
+            }
+            return a;
+        };
+        const CycleResult r1 = keyframe_cycle(true), i1 = keyframe_cycle(true, true), r2 = keyframe_cycle(true),
+                          i2 = keyframe_cycle(true, true);
+        const CycleResult r = pool(r1, r2), in = pool(i1, i2);
+        const CycleResult ev = keyframe_cycle(true, true, true);
+        // per cycle, ms: the face's structural uploads (host clock) and, inside ldso_ba_edit_window, the
+        // planner and the rest of the call (host clock); per edit, ms: the device time of the staging
+        // launches and of k_edit_gather (HIP events, from the run with events)
+        auto split_json = [](const CycleResult &c) {
+            char b[640];
+            const double n = c.cycles > 0 ? c.cycles : 1;
+            std::snprintf(b, sizeof(b),
+                          "{\"structural_uploads\": %.2f, \"read_back_ms\": %.4f, \"graph_walk_and_mirror_ms\": %.4f, "
+                          "\"frame_terms_ms\": %.4f, \"edit_or_reload_call_ms\": %.4f, \"follow_up_updates_ms\": %.4f, "
+                          "\"edit_planner_ms\": %.4f, \"edit_rest_of_call_ms\": %.4f}",
+                          c.split[0] / n, c.split[1] / n, c.split[2] / n, c.split[3] / n, c.split[4] / n, c.split[5] / n,
+                          c.lib[1] / n, c.lib[2] / n);
+            return std::string(b);
+        };
+        const double ne = ev.lib[0] > 0 ? ev.lib[0] : 1;
+        char buf[4096];
+        std::snprintf(buf, sizeof(buf),
+                      ", \"keyframe_cycle_incremental\": {\"what\": \"the resident keyframe_cycle with setIncrementalEdits off / on, "
+                      "alternated in one process, 2 x %d cycles each; split: host clock per cycle; device: HIP events per edit, "
+                      "from a further incremental run with kernel timing on\", \"resident\": {\"ok\": %s, \"ms_median\": %.6f, "
+                      "\"ms_min\": %.6f, \"ms_max\": %.6f, \"split\": %s}, \"incremental\": {\"ok\": %s, \"ms_median\": %.6f, "
+                      "\"ms_min\": %.6f, \"ms_max\": %.6f, \"edits_applied\": %ld, \"edits_fallen_back\": %ld, "
+                      "\"h2d_image_bytes_per_cycle\": %.1f, \"allocs_per_cycle\": %.3f, \"split\": %s}, "
+                      "\"device\": {\"ok\": %s, \"edits\": %.0f, \"staging_launches_ms_per_edit\": %.5f, "
+                      "\"k_edit_gather_ms_per_edit\": %.5f}}",
+                      reps, r.ok ? "true" : "false", r.med, r.lo, r.hi, split_json(r).c_str(), in.ok ? "true" : "false", in.med,
+                      in.lo, in.hi, in.edits, in.fallen, in.xfer[0], in.xfer[2], split_json(in).c_str(), ev.ok ? "true" : "false",
+                      ev.lib[0], ev.lib[4] / ne, ev.lib[5] / ne);
+        kc_inc_json = buf;
+    }
     // one device-to-device ingest of the tracker's new frame (event record / wait, the layout-3
     // kernel): back to back on the host clock, one synchronisation at the end
     double ingest_us = -1;
@@ -520,10 +611,10 @@ int main(int argc, char **argv) {
         "with the residual / point write-back\"}, "
         "\"c_abi_optimize\": {\"ms_per_optimize\": %.6f, \"ms_per_gn_iteration\": %.6f}, "
         "\"flag_loop\": {\"residuals\": %d, \"ms\": %.6f, \"device_passes\": %ld}, "
-        "\"keyframe_cycle\": %s}\n",
+        "\"keyframe_cycle\": %s%s}\n",
         n_its, reps, ok ? "true" : "false", ms_opt, ms_opt / n_its, n_its, its_default, (int)vr.size(), (int)ef->allPoints.size(),
         ms_shim_digest, ms_shim_vec, ms_shim_map, ms_shim_digest / n_its, ms_shim_digest / ms_opt, ms_shim_vec / ms_opt,
         toRemove.size(),
-        ms_full, ms_raw, ms_raw / n_its, nres, ms_flag, flag_passes, kc_json.c_str());
+        ms_full, ms_raw, ms_raw / n_its, nres, ms_flag, flag_passes, kc_json.c_str(), kc_inc_json.c_str());
     return ok ? 0 : 1;
 }

@@ -5,6 +5,7 @@
 #include <rccl/rccl.h>
 
 #include <atomic>
+#include <chrono>
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -208,6 +209,20 @@ struct ldso_ba_ctx {
     GraphBuf<float> d_img_stage;
     GraphBuf<int> d_img_flag;
     PinBuf<char> pin_img;
+    // ldso_ba_edit_window.  by_id: the last load named its frames by store id.  d_ed_state ... d_ed_pt:
+    // the other halves of the double buffers of d_rs_state, d_rs_flags, d_rs_energy, d_rs_newenergy
+    // and d_pt_data (the carried arrays are gathered into them, then the halves change places);
+    // d_ed_*_src the gather indices; d_ed_n* the compact upload of the new entries.  Grow-only.
+    bool by_id = false;
+    GraphBuf<int8_t> d_ed_state, d_ed_nstate;
+    GraphBuf<uint8_t> d_ed_flags, d_ed_nflags;
+    GraphBuf<float> d_ed_energy, d_ed_newenergy, d_ed_pt, d_ed_nenergy, d_ed_npt;
+    GraphBuf<int> d_ed_rs_src, d_ed_pt_src;
+    // ldso_ba_edit_stats: edits applied, host clock of the planner / of the rest of the call, and (with
+    // kernel timing on) the device time of the staging launches and of k_edit_gather between three events
+    double ed_stat[6] = {0, 0, 0, 0, 0, 0};
+    Event ed_ev[3];
+    bool ed_ev_pending = false;
     int64_t xfer[4] = {0, 0, 0, 0};  // ldso_ba_transfer_stats
     // timing-only events: no system-scope fence (its L2 write-back and invalidate would be timed, and
     // would slow the kernel after the start event)
