@@ -51,7 +51,10 @@
 //                     generation, the frame store, struct ldso_ba_ctx
 //   ba_launch.h       staged uploads, timed launches, image staging, the parameter fillers and the
 //                     launches several entry points share
-//   ldso_ba.hip       the C ABI and the helpers between its extern "C" blocks (loads, the pass, the
+//   ba_window.h       a laid-out window onto the device: the one table of the buffers a Layout sizes
+//                     (window_buffers), walked by load_impl (ldso_ba_load*) and by edit_impl
+//                     (ldso_ba_edit_window)
+//   ldso_ba.hip       the C ABI and the helpers between its extern "C" blocks (the pass, the
 //                     exchange, the device solve, the captured graphs)
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -91,6 +94,7 @@
 #include "edit_plan.h"
 #include "ba_context.h"
 #include "ba_launch.h"
+#include "ba_window.h"
 
 // =========================================================================================
 // C ABI
@@ -296,222 +300,6 @@ void *ldso_ba_stream(ldso_ba_ctx *c) { return c ? (void *)c->stream : nullptr; }
 }  // extern "C"
 
 namespace {
-// The device buffers of one load, allocated in call order (never fewer than one element, so every
-// pointer is valid); host arrays given with put() are uploaded by upload() once all are allocated.
-// The first failed allocation ends the list: later calls do nothing and rc keeps its code.
-struct LoadList {
-    ldso_ba_ctx *c;
-    int rc = 0;
-    std::vector<InBatch::Item> ups;
-    template <typename T>
-    void alloc(GraphBuf<T> &buf, size_t count) {
-        if (!rc) rc = buf.alloc(std::max<size_t>(1, count));
-    }
-    template <typename T, typename V>
-    void put(GraphBuf<T> &buf, const std::vector<V> &v) {
-        static_assert(sizeof(T) == sizeof(V), "uploaded as is");
-        alloc(buf, v.size());
-        if (!rc) ups.push_back({buf.p, v.data(), v.size() * sizeof(V)});
-    }
-    int upload() {
-        for (const InBatch::Item &u : ups)
-            if (!rc && u.bytes) HIP_TRY(hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
-        return rc;
-    }
-};
-
-// The host-side fields a layout fixes: the windows' descriptors and orders, the counts the launches
-// are sized by, and the cached host copies it makes stale.
-void adopt_layout(ldso_ba_ctx *c, Layout &L, int n_windows) {
-    c->wh = std::move(L.wh);
-    c->wd.assign(n_windows, WinDev());
-    // WinDev is WinDesc under the name the kernels' symbols carry (see WinDev): keep both, copy across
-    c->kp_max = 0;
-    for (int w = 0; w < n_windows; w++) {
-        static_cast<WinDesc &>(c->wd[w]) = L.wd[w];
-        c->kp_max = std::max(c->kp_max, L.wd[w].KP);
-    }
-    c->sys_host_valid = false;
-    c->energy_valid = false;
-    c->n_top_items = (int)L.top_items.size();
-    c->n_sc_items = (int)L.sc_items.size();
-    c->n_pairs = (int)L.pair_win.size();
-    c->n_frames = (int)L.frame_win.size();
-    c->max_frames = L.max_frames;
-    c->host_stitch = c->max_frames <= kHostStitchMaxN && !read_switches().stitch_records;
-    c->P_tot = (int)L.pt_host.size();
-    c->vec_total = L.vec_total;
-    c->R_tot = (int)L.rs_tgt.size();
-    c->sc_smem_max = L.smem_max;
-    c->sys_n = (size_t)L.sys_total;
-    c->n_sum_blocks = (int)L.sum_blocks.size();
-    c->ns_cache.clear();
-    c->ns_cache_null = -1;
-}
-
-// Store slot -> window position, device to device on the context stream, where the position does
-// not hold that slot's content already (fslot: the store slot of every frame position)
-int place_store_frames(ldso_ba_ctx *c, const std::vector<int> &fslot) {
-    const FrameStore &S = c->store;
-    c->img_tag.resize((size_t)c->n_frames, 0ull);
-    const size_t bytes = c->img.slot_bytes();
-    for (int p = 0; p < c->n_frames; p++) {
-        const unsigned long long seq = S.seq[fslot[p]];
-        if (c->img_tag[p] == seq) continue;
-        c->img_tag[p] = 0;
-        HIP_TRY(hipMemcpyAsync(c->d_img.p + (size_t)p * c->img.frame_stride, S.slot(fslot[p]), bytes,
-                               hipMemcpyDeviceToDevice, c->stream));
-        c->img_tag[p] = seq;
-        c->xfer[1] += (int64_t)bytes;
-    }
-    return 0;
-}
-
-// parent != nullptr: a marginalisation context over `ws[0]` whose frames are the parent's window
-// parent_win (images borrowed, not uploaded; priorF scaled by setting_idepthFixPriorMargFac)
-// frame_ids != nullptr (ldso_ba_load_frames): the windows' frames are resident in the frame store
-// under these ids, [sum N]; the windows' dI is not read
-int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32_t shard_rank, int32_t shard_count,
-              const ldso_ba_ctx *parent, int parent_win, const int64_t *frame_ids = nullptr) {
-    if (!c || n_windows < 1 || !ws) return fail(-1, "bad arguments");
-    if (shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return fail(-1, "bad shard");
-    const FrameStore &S = c->store;
-    if (frame_ids && S.cap == 0) return fail(LDSO_BA_ERR_FRAME_STORE, "no frame store: call ldso_ba_frames_reserve first");
-    Layout L;
-    int rc = build_layout(ws, n_windows, shard_rank, shard_count, c->item_order, c->top_chunk, parent != nullptr, L,
-                          frame_ids != nullptr);
-    if (rc) return rc;
-    // every frame must be resident before anything of the loaded state changes
-    std::vector<int> fslot;
-    if (frame_ids) {
-        size_t k = 0;
-        for (int w = 0; w < n_windows; w++) {
-            if (ws[w].width != S.lay.width || ws[w].height != S.lay.height)
-                return fail(LDSO_BA_ERR_FRAME_STORE, "window size differs from the frame store's");
-            for (int f = 0; f < ws[w].n_frames; f++, k++) {
-                const int s = S.find(frame_ids[k]);
-                if (s < 0)
-                    return fail(LDSO_BA_ERR_FRAME_STORE,
-                                "frame id " + std::to_string((long long)frame_ids[k]) + " is not resident in the frame store");
-                fslot.push_back(s);
-            }
-        }
-    }
-    c->th_host_valid = false;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->n_win = n_windows;
-    c->shard_count = shard_count;
-    c->pass_since_load = false;
-    c->x_stride = 0;
-    c->x_prun = 0;
-    c->marg = parent != nullptr;
-    c->by_id = frame_ids != nullptr;
-    c->img_ext = nullptr;
-    if (parent) {
-        c->img = parent->img;
-        c->img_mode_pref = parent->img.mode;
-        c->img_ext = parent->d_img.p + (size_t)parent->wd[parent_win].frame_base * parent->img.frame_stride;
-    } else {
-        // a load from the store runs in the store's layout, ldso_ba_load in the preferred one
-        c->img = image_layout(frame_ids ? S.lay.mode : c->img_mode_pref, ws[0].width, ws[0].height);
-    }
-    adopt_layout(c, L, n_windows);
-    const size_t P = (size_t)c->P_tot, R = (size_t)c->R_tot, nw = (size_t)n_windows, vt = (size_t)L.vec_total;
-    const std::vector<float> neg(R, -1.0f);  // rs_energy_wo: nothing evaluated yet
-    LoadList A{c};
-    A.put(c->d_wins, L.wd);
-    const size_t img_n = (size_t)c->n_frames * c->img.frame_stride;
-    if (c->marg) {
-        c->d_img.release();
-        c->img_tag.clear();
-    } else if (!frame_ids || !c->d_img.p || c->d_img.n < img_n) {
-        A.alloc(c->d_img, img_n);  // a new array (and ldso_ba_load's own images) invalidates the tags
-        c->xfer[2]++;
-        c->img_tag.clear();
-    }
-    if (c->marg) A.alloc(c->d_adhtd, (size_t)c->n_pairs * 8);
-    A.put(c->d_precalc, L.precalc);
-    A.put(c->d_frame_th, L.frame_th);
-    A.put(c->d_pt_data, L.pt_data);
-    A.alloc(c->d_pt_out, P * 12);
-    A.alloc(c->d_pt_step, P);
-    A.put(c->d_pt_host, L.pt_host);
-    A.put(c->d_adH, L.adH);
-    A.put(c->d_adT, L.adT);
-    A.put(c->d_pt_nres, L.pt_nres);
-    A.put(c->d_rs_slot, L.rs_slot);
-    A.put(c->d_pt_tgt, L.pt_tgt);
-    A.put(c->d_pair_win, L.pair_win);
-    A.put(c->d_frame_win, L.frame_win);
-    A.put(c->d_rs_tgt, L.rs_tgt);
-    A.put(c->d_rs_flags, L.rs_flags);
-    A.put(c->d_rs_state, L.rs_state);
-    A.alloc(c->d_rs_newstate, R);
-    A.put(c->d_rs_energy, L.rs_energy);
-    A.put(c->d_rs_newenergy, L.rs_energy);
-    A.put(c->d_rs_energy_wo, neg);
-    A.alloc(c->d_rs_center, R);
-    A.alloc(c->d_rec_a, (size_t)L.rec_base);
-    A.alloc(c->d_rec_b, (size_t)L.rec_base);
-    A.alloc(c->d_geo_snap, (size_t)c->n_pairs * kGeoSnap);
-    A.put(c->d_top_items, L.top_items);
-    A.put(c->d_sc_items, L.sc_items);
-    A.put(c->d_pair_items, L.pair_items);
-    A.put(c->d_host_items, L.host_items);
-    A.alloc(c->d_top_slab, L.top_items.size() * kTopVals);
-    A.alloc(c->d_sc_slab, (size_t)L.sc_slab_total);
-    A.alloc(c->d_item_energy, L.top_items.size() * 2);
-    A.alloc(c->d_sys, c->sys_n + 4 * nw);  // + win_energy() + win_nid()
-    A.alloc(c->d_stage, (size_t)L.stage_total);
-    A.put(c->d_sum_blocks, L.sum_blocks);
-    A.alloc(c->d_xad, nw * kXadStride);
-    A.alloc(c->d_prior, 2 * vt);
-    A.alloc(c->d_x, vt);
-    A.alloc(c->d_ns, 7 * vt);
-    A.alloc(c->d_ns_nm, 7 * vt);
-    A.alloc(c->d_ns_g, (size_t)kPrepGStride * nw);
-    A.put(c->d_pt_win, L.pt_win);
-    if ((rc = A.upload())) return rc;
-    HIP_TRY(hipMemsetAsync(c->d_rs_center.p, 0, c->d_rs_center.bytes(), c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_rec_a.p, 0, c->d_rec_a.bytes(), c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_rec_b.p, 0xFF, c->d_rec_b.bytes(), c->stream));  // NaN: not active
-    HIP_TRY(hipMemsetAsync(c->d_geo_snap.p, 0, c->d_geo_snap.bytes(), c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_pt_out.p, 0, c->d_pt_out.bytes(), c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_pt_step.p, 0, c->d_pt_step.bytes(), c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_sys.p, 0, c->d_sys.bytes(), c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_rs_newstate.p, LDSO_BA_RES_OUTLIER, c->d_rs_newstate.bytes(), c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    // images: per frame through a float3 staging buffer, repacked on the device; the
-    // intensity-only layout falls back to 2x4 float4 tiles if the caller's gradients are not
-    // makeImages' (then recomputing them would not be exact)
-    if (frame_ids) {
-        if ((rc = place_store_frames(c, fslot))) return rc;
-    } else if (!c->marg) {
-        int mismatch = 0;
-        rc = stage_images(c, ws, n_windows, &mismatch);
-        if (rc) return rc;
-        if (c->img.mode == 3 && mismatch) {
-            c->img_mode_pref = 1;  // for later loads and reserves too
-            c->img = image_layout(1, c->img.width, c->img.height);
-            rc = c->d_img.alloc((size_t)c->n_frames * c->img.frame_stride);
-            c->xfer[2]++;
-            if (rc) return rc;
-            rc = stage_images(c, ws, n_windows, &mismatch);
-            if (rc) return rc;
-        }
-    }
-    if (c->sc_smem_max > 64 * 1024) {
-        HIP_TRY(hipFuncSetAttribute((const void *)k_point_sc, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)c->sc_smem_max));
-    }
-    for (int w = 0; w < n_windows; w++) {
-        rc = upload_priors(c, w);
-        if (rc) return rc;
-    }
-    return 0;
-}
-
 // Device -> slot on the context stream, ordered by events and never by the host: the ingest waits for
 // what the producer's stream holds now (ev_prod), and whatever that stream is given later -- the
 // producer's next overwrite of its buffers -- waits for the ingest (ev_cons).  The slot itself is
@@ -542,218 +330,6 @@ int store_ingest_device(ldso_ba_ctx *c, int64_t id, const float *inten, const vo
     c->xfer[1] += (int64_t)l.slot_bytes();
     S.commit(slot, id);
     c->xfer[3]++;
-    return 0;
-}
-// ldso_ba_edit_window.  A buffer that is too small grows to half again its size, so that a cycle
-// whose counts wander (7 -> 6 -> 7 keyframes) stops allocating after its first round.
-template <typename T>
-int edit_grow(ldso_ba_ctx *c, GraphBuf<T> &b, size_t need) {
-    need = std::max<size_t>(need, 1);
-    if (b.p && b.n >= need) return 0;
-    c->xfer[2]++;  // ldso_ba_transfer_stats counts the edit's growths with the image allocations
-    return b.alloc(std::max(need, b.n + b.n / 2));
-}
-template <typename T>
-void swap_halves(GraphBuf<T> &a, GraphBuf<T> &b) {
-    std::swap(a.p, b.p);
-    std::swap(a.n, b.n);
-}
-inline size_t pad4(size_t n) { return (n + 3) & ~(size_t)3; }
-
-// the device times of the last timed edit into ed_stat (its events have been recorded on the stream)
-void edit_events_drain(ldso_ba_ctx *c) {
-    if (!c->ed_ev_pending) return;
-    c->ed_ev_pending = false;
-    float a = 0, b = 0;
-    if (hipEventSynchronize(c->ed_ev[2].e) == hipSuccess && hipEventElapsedTime(&a, c->ed_ev[0].e, c->ed_ev[1].e) == hipSuccess &&
-        hipEventElapsedTime(&b, c->ed_ev[1].e, c->ed_ev[2].e) == hipSuccess) {
-        c->ed_stat[4] += a;
-        c->ed_stat[5] += b;
-    }
-}
-
-int edit_impl(ldso_ba_ctx *c, int win, const ldso_ba_edit *e) {
-    if (!c || !e || !e->after || !e->frame_ids) return fail(-1, "bad arguments");
-    using EdClock = std::chrono::steady_clock;
-    const EdClock::time_point ed_t0 = EdClock::now();
-    if (c->n_win != 1 || win != 0) return fail(-1, "edit: the context must hold exactly one window (window 0)");
-    if (c->marg) return fail(-1, "edit: not on a marginalisation context");
-    if (c->shard_count > 1 || c->comm) return fail(-1, "edit: not on a sharded context");
-    if (!c->by_id) return fail(-1, "edit: the window was not loaded with ldso_ba_load_frames");
-    EditPlan plan;
-    int rc = plan_edit(c->wh[0], c->wd[0], *e, c->item_order, c->top_chunk, plan);
-    if (rc) return rc;
-    const EdClock::time_point ed_t1 = EdClock::now();
-    const ldso_ba_window &a = *e->after;
-    const FrameStore &S = c->store;
-    if (a.width != S.lay.width || a.height != S.lay.height)
-        return fail(LDSO_BA_ERR_FRAME_STORE, "window size differs from the frame store's");
-    std::vector<int> fslot;
-    for (int f = 0; f < a.n_frames; f++) {
-        const int s = S.find(e->frame_ids[f]);
-        if (s < 0)
-            return fail(LDSO_BA_ERR_FRAME_STORE,
-                        "frame id " + std::to_string((long long)e->frame_ids[f]) + " is not resident in the frame store");
-        fslot.push_back(s);
-    }
-    // ---- nothing is refused from here on ----
-    Layout &L = plan.L;
-    const size_t P = L.pt_host.size(), R = L.rs_tgt.size(), vt = (size_t)L.vec_total, np = L.pair_win.size();
-    const size_t n_new_r = plan.new_res.size(), n_new_p = plan.new_pts.size(), sys_n = (size_t)L.sys_total;
-    HIP_TRY(hipSetDevice(c->device));
-    const bool ed_timed = c->timer.on;
-    if (ed_timed) {
-        edit_events_drain(c);
-        for (Event &ev : c->ed_ev)
-            if ((rc = ev.ensure(hipEventDefault))) return rc;
-    }
-    const size_t img_n = L.frame_win.size() * c->img.frame_stride;
-    if (!c->d_img.p || c->d_img.n < img_n) {  // as a load: a new image array invalidates the tags
-        if ((rc = c->d_img.alloc(std::max(img_n, c->d_img.n + c->d_img.n / 2)))) return rc;
-        c->xfer[2]++;
-        c->img_tag.clear();
-    }
-    if ((rc = edit_grow(c, c->d_precalc, np * LDSO_BA_PRECALC_STRIDE)) || (rc = edit_grow(c, c->d_frame_th, L.frame_th.size())) ||
-        (rc = edit_grow(c, c->d_pt_out, P * 12)) || (rc = edit_grow(c, c->d_pt_step, P)) || (rc = edit_grow(c, c->d_pt_host, P)) ||
-        (rc = edit_grow(c, c->d_adH, np * 64)) || (rc = edit_grow(c, c->d_adT, np * 64)) || (rc = edit_grow(c, c->d_pt_nres, P)) ||
-        (rc = edit_grow(c, c->d_rs_slot, R)) || (rc = edit_grow(c, c->d_pt_tgt, P)) || (rc = edit_grow(c, c->d_pair_win, np)) ||
-        (rc = edit_grow(c, c->d_frame_win, L.frame_win.size())) || (rc = edit_grow(c, c->d_rs_tgt, pad4(R))) ||
-        (rc = edit_grow(c, c->d_rs_newstate, R)) || (rc = edit_grow(c, c->d_rs_energy_wo, R)) || (rc = edit_grow(c, c->d_rs_center, R)) ||
-        (rc = edit_grow(c, c->d_rec_a, (size_t)L.rec_base)) || (rc = edit_grow(c, c->d_rec_b, (size_t)L.rec_base)) ||
-        (rc = edit_grow(c, c->d_geo_snap, np * kGeoSnap)) || (rc = edit_grow(c, c->d_top_items, L.top_items.size())) ||
-        (rc = edit_grow(c, c->d_sc_items, L.sc_items.size())) || (rc = edit_grow(c, c->d_pair_items, L.pair_items.size())) ||
-        (rc = edit_grow(c, c->d_host_items, L.host_items.size())) || (rc = edit_grow(c, c->d_top_slab, L.top_items.size() * kTopVals)) ||
-        (rc = edit_grow(c, c->d_sc_slab, (size_t)L.sc_slab_total)) || (rc = edit_grow(c, c->d_item_energy, L.top_items.size() * 2)) ||
-        (rc = edit_grow(c, c->d_sys, sys_n + 4)) || (rc = edit_grow(c, c->d_stage, (size_t)L.stage_total)) ||
-        (rc = edit_grow(c, c->d_sum_blocks, L.sum_blocks.size())) || (rc = edit_grow(c, c->d_prior, 2 * vt)) ||
-        (rc = edit_grow(c, c->d_x, vt)) || (rc = edit_grow(c, c->d_ns, 7 * vt)) || (rc = edit_grow(c, c->d_ns_nm, 7 * vt)) ||
-        (rc = edit_grow(c, c->d_pt_win, P)) ||
-        // the other halves of the carried arrays, the gather indices, the new entries
-        (rc = edit_grow(c, c->d_ed_state, R)) || (rc = edit_grow(c, c->d_ed_flags, R)) || (rc = edit_grow(c, c->d_ed_energy, R)) ||
-        (rc = edit_grow(c, c->d_ed_newenergy, R)) || (rc = edit_grow(c, c->d_ed_pt, P * LDSO_BA_POINT_STRIDE)) ||
-        (rc = edit_grow(c, c->d_ed_rs_src, R)) || (rc = edit_grow(c, c->d_ed_pt_src, P)) ||
-        (rc = edit_grow(c, c->d_ed_nstate, pad4(n_new_r))) || (rc = edit_grow(c, c->d_ed_nflags, pad4(n_new_r))) ||
-        (rc = edit_grow(c, c->d_ed_nenergy, n_new_r)) || (rc = edit_grow(c, c->d_ed_npt, n_new_p * LDSO_BA_POINT_STRIDE)))
-        return rc;
-
-    // the old arrays and their size, before the layout is adopted
-    EditParams E{};
-    E.o_state = c->d_rs_state.p;
-    E.o_flags = c->d_rs_flags.p;
-    E.o_energy = c->d_rs_energy.p;
-    E.o_newenergy = c->d_rs_newenergy.p;
-    E.o_pt = reinterpret_cast<const float4 *>(c->d_pt_data.p);
-    c->th_host_valid = false;
-    c->pass_since_load = false;
-    c->x_stride = 0;
-    c->x_prun = 0;
-    adopt_layout(c, L, 1);
-
-    // the compact upload: the new points' records and the new residuals' state, energy and flags
-    std::vector<float> n_pt(n_new_p * LDSO_BA_POINT_STRIDE), n_en(n_new_r);
-    std::vector<int8_t> n_st(pad4(n_new_r), 0);
-    std::vector<uint8_t> n_fl(pad4(n_new_r), 0);
-    for (size_t i = 0; i < n_new_p; i++)
-        std::memcpy(&n_pt[i * LDSO_BA_POINT_STRIDE], a.point_data + (size_t)plan.new_pts[i] * LDSO_BA_POINT_STRIDE,
-                    LDSO_BA_POINT_STRIDE * sizeof(float));
-    for (size_t i = 0; i < n_new_r; i++) {
-        n_st[i] = a.res_state[plan.new_res[i]];
-        n_fl[i] = a.res_flags[plan.new_res[i]];
-        n_en[i] = a.res_energy[plan.new_res[i]];
-    }
-    L.rs_tgt.resize(pad4(R), 0);  // k_pack_out copies whole words
-    std::vector<double> pr;
-    priors_vector(c, 0, pr);
-    InBatch B;
-    auto put = [&B](void *dst, const auto &v) { B.add(dst, v.data(), v.size() * sizeof(v[0])); };
-    put(c->d_wins.p, L.wd);
-    put(c->d_precalc.p, L.precalc);
-    put(c->d_frame_th.p, L.frame_th);
-    put(c->d_pt_host.p, L.pt_host);
-    put(c->d_adH.p, L.adH);
-    put(c->d_adT.p, L.adT);
-    put(c->d_pt_nres.p, L.pt_nres);
-    put(c->d_rs_slot.p, L.rs_slot);
-    put(c->d_pt_tgt.p, L.pt_tgt);
-    put(c->d_pair_win.p, L.pair_win);
-    put(c->d_frame_win.p, L.frame_win);
-    put(c->d_rs_tgt.p, L.rs_tgt);
-    put(c->d_top_items.p, L.top_items);
-    put(c->d_sc_items.p, L.sc_items);
-    put(c->d_pair_items.p, L.pair_items);
-    put(c->d_host_items.p, L.host_items);
-    put(c->d_sum_blocks.p, L.sum_blocks);
-    put(c->d_pt_win.p, L.pt_win);
-    put(c->d_prior.p, pr);
-    put(c->d_ed_rs_src.p, plan.rs_gather);
-    put(c->d_ed_pt_src.p, plan.pt_gather);
-    put(c->d_ed_nstate.p, n_st);
-    put(c->d_ed_nflags.p, n_fl);
-    put(c->d_ed_nenergy.p, n_en);
-    put(c->d_ed_npt.p, n_pt);
-    if (ed_timed) HIP_TRY(hipEventRecord(c->ed_ev[0].e, c->stream));
-    if ((rc = B.flush(c))) return rc;
-    if (ed_timed) HIP_TRY(hipEventRecord(c->ed_ev[1].e, c->stream));
-
-    E.rs_src = c->d_ed_rs_src.p;
-    E.pt_src = c->d_ed_pt_src.p;
-    E.n_state = c->d_ed_nstate.p;
-    E.n_flags = c->d_ed_nflags.p;
-    E.n_energy = c->d_ed_nenergy.p;
-    E.n_pt = reinterpret_cast<const float4 *>(c->d_ed_npt.p);
-    E.state = c->d_ed_state.p;
-    E.flags = c->d_ed_flags.p;
-    E.energy = c->d_ed_energy.p;
-    E.newenergy = c->d_ed_newenergy.p;
-    E.pt = reinterpret_cast<float4 *>(c->d_ed_pt.p);
-    E.newstate = c->d_rs_newstate.p;
-    E.R = (int)R;
-    E.P = (int)P;
-    // what ldso_ba_load fills: centres, records (rec_b NaN: not active), geometry snapshots, point
-    // outputs and steps, the packed system with its energy and sumNID slots, nothing evaluated yet
-    auto fill = [&E](void *dst, size_t words, unsigned v) {
-        E.fill_dst[E.n_fill] = static_cast<unsigned *>(dst);
-        E.fill_words[E.n_fill] = (long long)words;
-        E.fill_val[E.n_fill++] = v;
-    };
-    const float minus_one = -1.0f;
-    unsigned minus_one_bits;
-    std::memcpy(&minus_one_bits, &minus_one, 4);
-    fill(c->d_rs_center.p, R * 4, 0u);
-    fill(c->d_rec_a.p, (size_t)L.rec_base * 4, 0u);
-    fill(c->d_rec_b.p, (size_t)L.rec_base * 2, 0xFFFFFFFFu);
-    fill(c->d_geo_snap.p, np * kGeoSnap, 0u);
-    fill(c->d_pt_out.p, P * 12, 0u);
-    fill(c->d_pt_step.p, P, 0u);
-    fill(c->d_sys.p, (sys_n + 4) * 2, 0u);
-    fill(c->d_rs_energy_wo.p, R, minus_one_bits);
-    static_assert(kEditFills >= 8, "one slot per fill above");
-    size_t work = std::max(R, P * kPtVec);
-    for (int f = 0; f < E.n_fill; f++) work = std::max(work, (size_t)E.fill_words[f]);
-    const int nb = (int)std::min<size_t>(1024, (work + 255) / 256 + 1);
-    k_edit_gather<<<nb, 256, 0, c->stream>>>(E);
-    HIP_TRY(hipGetLastError());
-    if (ed_timed) {
-        HIP_TRY(hipEventRecord(c->ed_ev[2].e, c->stream));
-        c->ed_ev_pending = true;
-    }
-    // the gathered halves become the context's arrays; captured graphs hold the old addresses
-    swap_halves(c->d_rs_state, c->d_ed_state);
-    swap_halves(c->d_rs_flags, c->d_ed_flags);
-    swap_halves(c->d_rs_energy, c->d_ed_energy);
-    swap_halves(c->d_rs_newenergy, c->d_ed_newenergy);
-    swap_halves(c->d_pt_data, c->d_ed_pt);
-    BumpAllocGen::changed();
-    if ((rc = place_store_frames(c, fslot))) return rc;
-    if (c->sc_smem_max > 64 * 1024) {
-        HIP_TRY(hipFuncSetAttribute((const void *)k_point_sc, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)c->sc_smem_max));
-    }
-    const EdClock::time_point ed_t2 = EdClock::now();
-    c->ed_stat[0] += 1;
-    c->ed_stat[1] += std::chrono::duration<double, std::milli>(ed_t1 - ed_t0).count();
-    c->ed_stat[2] += std::chrono::duration<double, std::milli>(ed_t2 - ed_t1).count();
-    c->ed_stat[3] += std::chrono::duration<double, std::milli>(ed_t2 - ed_t0).count();
     return 0;
 }
 }  // namespace

@@ -229,7 +229,11 @@ int main() {
         good("insert points", cut(pl, f4, [](int p) { return p % 5 != 0; }, all_rs, ranked), base);
         good("everything new", cut(pl, f4, [](int p) { return p % 2 == 0; }, all_rs, ranked),
              cut(pl, f4, [](int p) { return p % 2 == 1; }, all_rs, ranked));
-        good("no points left", base, cut(pl, f4, [](int) { return false; }, all_rs, ranked));
+        const Win none = cut(pl, f4, [](int) { return false; }, all_rs, ranked);
+        good("no points left", base, none);
+        good("from empty", none, base);
+        good("empty to empty", none, none);
+        good("points without residuals", base, cut(pl, f4, all_pt, [](int, int) { return false; }, ranked));
     }
     const Win base = cut(pl, f4, all_pt, all_rs);
     const Win dropped = cut(pl, f4, all_pt, [](int p, int t) { return (p + t) % 3 != 0; });

@@ -165,6 +165,23 @@ def edit_identity(pool, sel):
     return Sel(sel.frames, sel.pts)
 
 
+def edit_no_points(pool, sel):
+    """(l) the frames alone: P = R = 0."""
+    return Sel(sel.frames, [])
+
+
+def edit_no_residuals(pool, sel):
+    """(m) every point kept, every residual dropped: P > 0, R = 0."""
+    return Sel(sel.frames, [(p, []) for p, _ in sel.pts])
+
+
+# windows without residuals: a pass runs on them, ldso_ba_iterate has nothing to solve for
+DEGENERATE = {
+    "l_no_points": edit_no_points,
+    "m_no_residuals": edit_no_residuals,
+}
+
+
 EDITS = {
     "a_drop": edit_drop,
     "b_remove_host": edit_remove_host,

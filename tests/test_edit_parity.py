@@ -164,6 +164,28 @@ def test_two_edits_in_a_row(built):
     B.close()
 
 
+@pytest.mark.parametrize("name", list(ec.DEGENERATE))
+def test_edit_to_a_window_without_residuals_and_back(built, name):
+    """(l), (m) a zero through every part of the edit and of the load: counts of 0, uploads of 0 bytes,
+    fills of 0 words, then growth from the one-element minimum.  The base window is edited to one
+    with no residuals (and, in (l), no points) and a pass runs -- compared after the pass only, since
+    ldso_ba_iterate has nothing to solve for there; then it is edited back to the base selection,
+    where every residual (in (l) every point too) is new.  B follows by reloads."""
+    pool = ec.make_pool()
+    s0 = ec.base_sel(pool)
+    s1 = ec.DEGENERATE[name](pool, s0)
+    assert sum(len(items) for _, items in s1.pts) == 0 and (len(s1.pts) == 0) == (name == "l_no_points")
+    A, B = loaded_pair(pool, s0)
+    edit_and_reload(pool, A, B, s0, s1)
+    for c in (A, B):
+        c.linearize(fix=False, accumulate=True)
+    compare(A, B, f"{name}, pass")
+    edit_and_reload(pool, A, B, s1, s0)
+    pass_and_iterate(A, B, f"{name} and back")
+    A.close()
+    B.close()
+
+
 def test_keyframe_cycle_moves_no_image_and_stops_allocating(built):
     """(k) N = 7 -> 6 -> 7 at an S7 window's point count, twice.  The first cycle drops the oldest frame
     and appends a new one (image positions shift: device-to-device copies only); the second drops the
