@@ -283,6 +283,49 @@ public:
     // HM += margWeightFac H, bM += margWeightFac b, removePoint, makeIDX
     void marginalizePointsF();
     void dropPointsF();  // removes the points with status OUTLIER or OUT
+
+    // ---- closing a keyframe on the device ----------------------------------------------------
+    // FullSystem::removeOutliers + flagPointsForRemoval's decision (FullSystem.cc:1356-1424, :1654,
+    // PointHessian::isOOB / isInlierNew) for every point of the loaded window in one device call
+    // (ldso_ba_flag_points), from the residual states and the points' idepth_hessian where the last
+    // pass left them; no residual is read back.  To be called after linearizeAll(true), before the
+    // structural changes that follow from it (the window the fix pass ran on must still be the
+    // face's; otherwise ok stays false and lastError() says so).  Arrays in allPoints order:
+    //   frameFlagged [nFrames]  FrameHessian::flaggedForMarginalization (empty: read from `frames`)
+    //   numGood [P]             PointHessian::numGoodResiduals before that linearizeAll(true)
+    //   lastRes [2 P]           PointFrameResidual::mirrorIdx of lastResiduals[i].first, or -1
+    //   lastState [2 P]         the retained lastResiduals[i].second, read where lastRes is -1
+    // Sets every point's status and returns, as FixPassResult does: toRemove (the residuals that are
+    // not active: removeOutliers' and the reductor's, for ef->dropResidual), numGood (the new
+    // numGoodResiduals), lastState (lastResiduals[i].second), and the points per status.  The caller
+    // then drops toRemove, calls dropPointsF and marginalizePointsF as the reference does.
+    struct FlagResult {
+        bool ok = false;
+        std::vector<PointFrameResidual *> toRemove;
+        std::vector<int> numGood;
+        std::vector<int8_t> lastState;
+        int counts[4] = {0, 0, 0, 0};  // ACTIVE, OUTLIER, OUT, MARGINALIZED
+    };
+    FlagResult flagPoints(const ldso_ba_flag_params *params, const std::vector<uint8_t> &frameFlagged,
+                          const std::vector<int32_t> &numGood, const std::vector<int32_t> &lastRes,
+                          const std::vector<int8_t> &lastState);
+    // Device marginalisation (default off; needs incremental edits): marginalizePointsF builds its
+    // second context from the loaded window's device arrays (ldso_ba_load_marginalization_device:
+    // the MARGINALIZED points' records and their remaining residuals' state, gathered device to
+    // device) instead of packing them from the objects, and does not read the window's residuals
+    // back first; only the marginalisation context's residual results come back, for isLinearized and
+    // connectivityMap.  The loaded window is then still the one before the keyframe's structural
+    // changes, and one ldso_ba_edit_window applies them all at the next pass.  Where the device does
+    // not hold what the host path would send -- a residual of such a point inserted since the load,
+    // residual states or point values edited on the host and not yet uploaded, a window not loaded
+    // with incremental edits on, a load the library refuses -- the call takes the host path.
+    void setDeviceMarginalization(bool on) { deviceMarg_ = on; }
+    bool deviceMarginalization() const { return deviceMarg_; }
+    long deviceMarginalizations() const { return deviceMargs_; }  // marginalizePointsF calls served that way
+    // full read-backs of the loaded window's residual arrays into the objects so far (syncResiduals:
+    // before a residual method, resetOOB, a structural change without incremental edits, the host
+    // path of marginalizePointsF); the compact per-pass summary of linearizeAll is not one
+    long residualReadBacks() const { return readBacks_; }
     // the non-VI branch (setting_vi_enable = false is the only setting setSettings accepts): the
     // reference's fourth argument, the InertialHessian, has no counterpart here and must be null
     void solveSystemF(int iteration, double lambda, shared_ptr<CalibHessian> HCalib);
@@ -463,6 +506,12 @@ private:
         if (incremental_ && m >= 0 && (size_t)m < resPtr_.size() && resPtr_[m] == r) resPtr_[m] = nullptr;
     }
     long editsApplied_ = 0, editsFallenBack_ = 0;
+    bool deviceMarg_ = false;
+    long deviceMargs_ = 0, readBacks_ = 0;
+    bool marginalizeFromDevice();  // false: not possible here, take the host path
+    void frameTermsWindow(ldso_ba_window &w);
+    void applyMarginalization(const std::vector<PointFrameResidual *> &res, const std::vector<double> &H,
+                              const std::vector<double> &b);
     std::vector<int> loadedIds_;
     std::unordered_map<const PointHessian *, int> mirrorPoint_;
     int storeW_ = 0, storeH_ = 0;

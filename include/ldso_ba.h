@@ -405,6 +405,98 @@ int ldso_ba_load_marginalization(ldso_ba_ctx *marg, const ldso_ba_ctx *parent, i
  * points of `marg` are readable with get_residuals / get_points as after a pass. */
 int ldso_ba_marginalize_points(ldso_ba_ctx *marg, const float *ad_ht_delta, double *H, double *b);
 
+/* ---- closing a keyframe on the device --------------------------------------------------
+ * FullSystem::makeKeyFrame's removeOutliers -> flagPointsForRemoval -> marginalizePointsF
+ * (FullSystem.cc:606-634) without reading a residual array back: ldso_ba_flag_points classifies the
+ * points of a loaded window where its residual states live, ldso_ba_load_marginalization_device
+ * builds the marginalisation context from the loaded window's device arrays, and
+ * ldso_ba_marginalize_points and ldso_ba_edit_window do the rest as they stand. */
+
+/* Point::PointStatus as flagPointsForRemoval leaves it (FullSystem.cc:1356-1424) */
+#define LDSO_BA_PT_ACTIVE 0
+#define LDSO_BA_PT_OUTLIER 1
+#define LDSO_BA_PT_OUT 2
+#define LDSO_BA_PT_MARGINALIZED 3
+
+typedef struct ldso_ba_flag_params {
+    int32_t min_good_active_res_for_marg; /* setting_minGoodActiveResForMarg (3, Setting.cc)  */
+    int32_t min_good_res_for_marg;        /* setting_minGoodResForMarg (4)                     */
+    float min_idepth_h_marg;              /* setting_minIdepthH_marg (50)                      */
+    int32_t reserved_;                    /* 0 */
+} ldso_ba_flag_params;
+/* Writes Setting.cc's 3, 4 and 50 into *p. */
+void ldso_ba_default_flag_params(ldso_ba_flag_params *p);
+
+/* The decision of removeOutliers (FullSystem.cc:1654) and flagPointsForRemoval (:1356-1424, with
+ * PointHessian::isOOB / isInlierNew, PointHessian.h:53-78) for every point of window `win`, from the
+ * residual states, flags, point records and idepth_hessian as the device holds them (normally after
+ * the fix pass, ldso_ba_linearize(fix = 1)) and the per-point bookkeeping the frontend keeps.
+ * params: NULL = the defaults.  Inputs, host arrays in the caller's order:
+ *   frame_flagged [N]   FrameHessian::flaggedForMarginalization
+ *   num_good [P]        PointHessian::numGoodResiduals before the last linearizeAll(true)
+ *   last_res [P][2]     the index in the loaded window of lastResiduals[i].first, or -1
+ *   last_state [P][2]   the retained lastResiduals[i].second, read only where last_res is -1 (may be
+ *                       NULL if no entry is -1)
+ * With k over the residuals of point p: live(k) = flags[k] & LDSO_BA_FLAG_ACTIVE (the reductor's
+ * isActive() test, FullSystem.cc:1795-1820; a residual that is not live counts as dropped),
+ * n_live = sum live(k), vis = the live residuals with state IN whose target is flagged,
+ * ls[i] = state[last_res[p][i]] or last_state[p][i] (FullSystem.cc:1745-1751), ng = num_good[p] +
+ * n_live (isNew is never cleared, so every active residual of the fix pass adds one, :1800-1814),
+ * A / G = min_good_active_res_for_marg / min_good_res_for_marg:
+ *   1. idepth_scaled < 0 || n_live == 0                                   -> OUTLIER
+ *   2. oob = (n_live >= A && ng > G + 10 && n_live - vis < A) || ls[0] == OOB
+ *            || (n_live >= 2 && ls[0] == OUTLIER && ls[1] == OUTLIER)
+ *   3. oob || frame_flagged[host]: n_live >= A && ng >= G && idepth_hessian > min_idepth_h_marg
+ *                                                                         -> MARGINALIZED, else OUT
+ *   4. otherwise                                                          -> ACTIVE
+ * idepth_hessian is what ldso_ba_get_points would report at the time of the call.
+ * Outputs, caller order, any may be NULL: status [P] (LDSO_BA_PT_*), res_live [R] (the complement
+ * of removeOutliers' toRemove), num_good_out [P] (ng), last_state_out [P][2] (ls), counts [4]
+ * (points per status).
+ * The call only reads the context: states, records, point outputs and the last pass's results are
+ * bit for bit what they were.  All its counts are integers, so the result does not depend on the
+ * execution order.  One upload and one download of a few bytes per point and residual, one
+ * synchronisation; its staging grows only.
+ * Refused (< 0 with a message, before anything is launched): a sharded context or one with a
+ * communicator; a marginalisation context; a last_res entry that is neither -1 nor a residual of
+ * its own point. */
+int ldso_ba_flag_points(ldso_ba_ctx *ctx, int32_t win, const ldso_ba_flag_params *params,
+                        const uint8_t *frame_flagged, const int32_t *num_good, const int32_t *last_res,
+                        const int8_t *last_state, int8_t *status, uint8_t *res_live, int32_t *num_good_out,
+                        int8_t *last_state_out, int32_t *counts);
+
+/* ldso_ba_load_marginalization with the point records and the residuals' state, energy and flags
+ * taken from the parent's device arrays (the records ldso_ba_optimize stepped, the states of the
+ * last pass) instead of a host window:
+ *   frame_terms  an ldso_ba_window of which only the frame-level fields ldso_ba_load_marginalization
+ *                reads are read: n_frames, width, height, calib, frame_energy_th, precalc, ad_host,
+ *                ad_target, c_prior, c_delta, frame_prior, frame_delta_prior
+ *   points       [n_points] distinct point indices of the parent's window (caller order); their
+ *                order is the marginalisation window's caller order.  n_points == 0 is a valid load
+ *                (ldso_ba_marginalize_points then returns zero H and b)
+ *   res_live     [parent R] or NULL: which residuals of the chosen points the window holds, in the
+ *                parent's order (NULL: all of them)
+ * The marginalisation context is then, bit for bit, the one ldso_ba_load_marginalization makes from
+ * a host window filled with ldso_ba_get_point_data / ldso_ba_get_residuals read-backs of the
+ * parent: the host lays the selected structure out as a load does, the device gathers.  priorF is
+ * scaled by setting_idepthFixPriorMargFac as there.  The two contexts' streams are ordered by
+ * events.
+ * Refused (< 0 with a message): a point index out of range or given twice; a sharded parent or one
+ * with a communicator; LDSO_BA_TUNE_ITEM_ORDER 2 on `marg` (its order depends on a float sort of
+ * the point records); and what ldso_ba_load_marginalization refuses. */
+int ldso_ba_load_marginalization_device(ldso_ba_ctx *marg, const ldso_ba_ctx *parent, int32_t parent_win,
+                                        const ldso_ba_window *frame_terms, int32_t n_points, const int32_t *points,
+                                        const uint8_t *res_live);
+/* The host planner of ldso_ba_load_marginalization_device alone, no GPU needed (tests): `parent` is
+ * laid out as ldso_ba_load lays it out, the selection is planned against it, and per device-order
+ * residual / point of the marginalisation window its device position in the parent is returned
+ * (res_gather [selected R], point_gather [n_points]; either may be NULL).  *n_res_out (may be NULL)
+ * is the selected residual count.  *n_mismatch (may be NULL) is the number of index arrays in which
+ * the plan's layout differs from build_layout of the explicit marginalisation window. */
+int ldso_ba_marg_plan_check(const ldso_ba_window *parent, int32_t n_points, const int32_t *points,
+                            const uint8_t *res_live, int32_t item_order, int32_t top_chunk, int32_t *res_gather,
+                            int32_t *point_gather, int32_t *n_res_out, int32_t *n_mismatch);
+
 /* ---- point activation ----
  * FullSystem::optimizeImmaturePoint(point, min_obs, residuals) (FullSystem.cc:1035-1156) for n
  * immature points of window `win`: ImmaturePoint::linearizeResidual (ImmaturePoint.cc:319-389)

@@ -113,6 +113,25 @@ class LdsoBaEdit(C.Structure):
                 ("res_src", i32p)]
 
 
+# Point::PointStatus as ldso_ba_flag_points leaves it (LDSO_BA_PT_*)
+PT_ACTIVE, PT_OUTLIER, PT_OUT, PT_MARGINALIZED = 0, 1, 2, 3
+
+
+class FlagParams(C.Structure):
+    """ldso_ba_flag_params: setting_minGoodActiveResForMarg, setting_minGoodResForMarg,
+    setting_minIdepthH_marg (Setting.cc: 3, 4, 50)."""
+    _fields_ = [("min_good_active_res_for_marg", C.c_int32), ("min_good_res_for_marg", C.c_int32),
+                ("min_idepth_h_marg", C.c_float), ("reserved_", C.c_int32)]
+
+    @classmethod
+    def default(cls, **kw):
+        s = cls()
+        lib().ldso_ba_default_flag_params(C.byref(s))
+        for k, v in kw.items():
+            setattr(s, k, v)
+        return s
+
+
 def source_sha256() -> str | None:
     """sha256 over the sources libldso_ba.so is built from (ldso_amd/csrc, include/ldso_ba.h,
     include/ldso_ct.h): the identity of a build that survives a rebuild on another machine (the .so
@@ -229,6 +248,12 @@ ABI = [
     ("ldso_ba_edit_stats", C.c_int, [C.c_void_p, f64p]),
     ("ldso_ba_edit_plan_check", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, i32p, i32p, i32p, i32p, i32p,
                                           i32p, i32p]),
+    # closing a keyframe on the device
+    ("ldso_ba_default_flag_params", None, [C.c_void_p]),
+    ("ldso_ba_flag_points", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, u8p, i32p, i32p, i8p, i8p, u8p, i32p, i8p, i32p]),
+    ("ldso_ba_load_marginalization_device", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(LdsoBaWindow), C.c_int32, i32p, u8p]),
+    ("ldso_ba_marg_plan_check", C.c_int, [C.c_void_p, C.c_int32, i32p, u8p, C.c_int32, C.c_int32, i32p, i32p, i32p, i32p]),
 ]
 ERR_FRAME_STORE, ERR_GRADIENT_MISMATCH = -4, -5
 

@@ -227,6 +227,63 @@ class BAContext:
         window._keep = []
         return self
 
+    def load_marginalization_device(self, parent: "BAContext", parent_win: int, frame_terms: Window, points, res_live=None):
+        """ldso_ba_load_marginalization_device: this context becomes the marginalisation context of
+        `parent`'s window `parent_win` for its points `points` (distinct caller indices, whose order is
+        the marginalisation window's) and those of their residuals that res_live [parent R] selects
+        (None: all), the point records and the residuals' state, energy and flags gathered from the
+        parent's device arrays.  frame_terms: a Window of which only the frame-level fields are read
+        (the parent's own window will do).  self.windows[0] is the selection's structure: its
+        point_data / res_state / res_energy / res_flags are placeholders, the device holds the values."""
+        pw = parent.windows[parent_win]
+        pts = np.ascontiguousarray(np.asarray(points).reshape(-1), np.int32)
+        live = None if res_live is None else np.ascontiguousarray(res_live, np.uint8)
+        assert live is None or live.size == pw.n_residuals, "res_live has one entry per residual of the parent"
+        s = frame_terms.c_struct(with_images=False)
+        L.check(self._lib.ldso_ba_load_marginalization_device(self._h, parent._h, int(parent_win), C.byref(s), int(pts.size),
+                                                              L.ptr(pts, L.i32p), L.ptr(live, L.u8p)))
+        # the selection as a Window, so that residuals() / points() size their outputs
+        b0 = np.asarray(pw.point_res_begin, np.int64)[pts]
+        n = np.asarray(pw.point_res_begin, np.int64)[pts + 1] - b0
+        ks = np.repeat(b0 - (np.cumsum(n) - n), n) + np.arange(int(n.sum()))  # the points' residuals, in the list's order
+        owner = np.repeat(np.arange(pts.size), n)
+        if live is not None:
+            owner, ks = owner[live[ks] != 0], ks[live[ks] != 0]
+        begin = np.concatenate([[0], np.cumsum(np.bincount(owner, minlength=pts.size))]).astype(np.int32)
+        w = Window(n_frames=frame_terms.n_frames, width=frame_terms.width, height=frame_terms.height,
+                   calib=frame_terms.calib.copy(), frames=frame_terms.frames, dI=None,
+                   frame_energy_th=frame_terms.frame_energy_th, point_host=pw.point_host[pts].astype(np.int32),
+                   point_data=np.zeros((pts.size, L.POINT_STRIDE), np.float32), point_res_begin=begin,
+                   res_target=np.asarray(pw.res_target)[ks].astype(np.int32), res_state=np.zeros(ks.size, np.int8),
+                   res_energy=np.zeros(ks.size, np.float32), res_flags=np.zeros(ks.size, np.uint8),
+                   settings=frame_terms.settings)
+        self.windows = [w]
+        self._structs = s
+        self._parent = parent  # the borrowed images must outlive this context
+        return self
+
+    def flag_points(self, frame_flagged, num_good, last_res, last_state=None, params=None, win: int = 0) -> dict:
+        """ldso_ba_flag_points: removeOutliers' and flagPointsForRemoval's decision for every point of
+        window `win` from the device's residual states, flags, point records and idepth_hessian.
+        frame_flagged [N], num_good [P], last_res [P][2] (residual index in the window or -1),
+        last_state [P][2] (read where last_res is -1); params: an L.FlagParams (None = the defaults).
+        -> status [P] (L.PT_*), res_live [R], num_good [P], last_state [P][2], counts [4]."""
+        w = self.windows[win] if 0 <= win < len(self.windows) else None
+        P, R = (w.n_points, w.n_residuals) if w is not None else (0, 0)
+        ff = np.ascontiguousarray(frame_flagged, np.uint8)
+        ng = np.ascontiguousarray(num_good, np.int32)
+        lr = np.ascontiguousarray(last_res, np.int32).reshape(-1, 2)
+        ls = None if last_state is None else np.ascontiguousarray(last_state, np.int8).reshape(-1, 2)
+        assert w is None or (ff.size == w.n_frames and ng.size == P and lr.shape[0] == P and (ls is None or ls.shape[0] == P))
+        o = dict(status=np.zeros(P, np.int8), res_live=np.zeros(R, np.uint8), num_good=np.zeros(P, np.int32),
+                 last_state=np.zeros((P, 2), np.int8), counts=np.zeros(4, np.int32))
+        L.check(self._lib.ldso_ba_flag_points(self._h, int(win), C.byref(params) if params is not None else None,
+                                              L.ptr(ff, L.u8p), L.ptr(ng, L.i32p), L.ptr(lr, L.i32p), L.ptr(ls, L.i8p),
+                                              L.ptr(o["status"], L.i8p), L.ptr(o["res_live"], L.u8p),
+                                              L.ptr(o["num_good"], L.i32p), L.ptr(o["last_state"], L.i8p),
+                                              L.ptr(o["counts"], L.i32p)))
+        return o
+
     def marginalize_points(self, ad_ht_delta):
         """ldso_ba_marginalize_points -> (H, b) = (M - Msc, Mb - Mbsc) (EnergyFunctional.cc:226-243)."""
         n = self.windows[0].dim

@@ -440,26 +440,52 @@ void EnergyFunctional::removePoint(shared_ptr<PointHessian> ph) {
     epoch_++;
 }
 
-// EnergyFunctional.cc:205-262 with FullSystem.cc:1384-1404 (see the header)
-void EnergyFunctional::marginalizePointsF() {
-    epoch_++;
-    residualTouched();
-    allPointsToMarg.clear();
-    for (const shared_ptr<PointHessian> &p : registry_)
-        if (p->status == PointStatus::MARGINALIZED && !p->alreadyRemoved) allPointsToMarg.push_back(p);
-    if (allPointsToMarg.empty()) return;
-    if (!upload()) return;  // current frame terms; the parent window lends its device images
-    if (!margCtx_ && ldso_ba_create(device_, &margCtx_)) {
-        margCtx_ = nullptr;
-        fail("ldso_ba_create (marginalisation)");
-        return;
+// ldso_ba_flag_points on the loaded window (see the header)
+EnergyFunctional::FlagResult EnergyFunctional::flagPoints(const ldso_ba_flag_params *params,
+                                                          const std::vector<uint8_t> &frameFlagged,
+                                                          const std::vector<int32_t> &numGood,
+                                                          const std::vector<int32_t> &lastRes,
+                                                          const std::vector<int8_t> &lastState) {
+    FlagResult out;
+    if (!ctx_) {
+        if (err_.empty()) err_ = "flagPoints: no device context";
+        return out;
     }
-    // the parent window as loaded holds every point still flagged ACTIVE before this call
-    std::vector<PointHessian *> pts;
-    for (const shared_ptr<PointHessian> &p : allPointsToMarg) pts.push_back(p.get());
-    PointPack pk;
-    pk.build(pts);
-    ldso_ba_window w;
+    if (dirty_ || resSync_ == ResSync::HostNewer) {
+        err_ = "flagPoints: the window changed since the last pass (call it after linearizeAll(true), before the "
+               "structural changes and residual edits that follow)";
+        return out;
+    }
+    const size_t P = ptPtr_.size(), R = resPtr_.size(), N = frames.size();
+    if (numGood.size() != P || lastRes.size() != 2 * P || (!lastState.empty() && lastState.size() != 2 * P) ||
+        (!frameFlagged.empty() && frameFlagged.size() != N)) {
+        err_ = "flagPoints: array sizes do not match the window (allPoints order: numGood [P], lastRes / lastState [2 P])";
+        return out;
+    }
+    std::vector<uint8_t> ff(frameFlagged);
+    if (ff.empty())
+        for (const shared_ptr<FrameHessian> &f : frames) ff.push_back(f->flaggedForMarginalization ? 1 : 0);
+    std::vector<int8_t> status(P);
+    std::vector<uint8_t> live(R);
+    std::vector<int32_t> ng(P), counts(4, 0);
+    out.lastState.assign(2 * P, -1);
+    if (ldso_ba_flag_points(ctx_, 0, params, ff.data(), numGood.data(), lastRes.data(),
+                            lastState.empty() ? nullptr : lastState.data(), status.data(), live.data(), ng.data(),
+                            out.lastState.data(), counts.data())) {
+        fail("ldso_ba_flag_points");
+        return out;
+    }
+    for (size_t q = 0; q < P; q++) ptPtr_[q]->status = (PointStatus)status[q];  // LDSO_BA_PT_* are PointStatus' values
+    for (size_t k = 0; k < R; k++)
+        if (!live[k]) out.toRemove.push_back(resPtr_[k]);
+    out.numGood.assign(ng.begin(), ng.end());
+    for (int i = 0; i < 4; i++) out.counts[i] = counts[i];
+    out.ok = true;
+    return out;
+}
+
+// the frame-level fields of an ldso_ba_window, from the terms uploadFrameTerms computed last
+void EnergyFunctional::frameTermsWindow(ldso_ba_window &w) {
     std::memset(&w, 0, sizeof(w));
     w.n_frames = nFrames;
     w.width = width_;
@@ -473,21 +499,16 @@ void EnergyFunctional::marginalizePointsF() {
     w.c_delta = cDeltaF;
     w.frame_prior = fPrior_.data();
     w.frame_delta_prior = fDeltaPrior_.data();
-    pk.into(w);
+}
+
+// marginalizePointsF's tail (EnergyFunctional.cc:244-262): res are the marginalisation context's
+// residuals with its results read into them, (H, b) its system
+void EnergyFunctional::applyMarginalization(const std::vector<PointFrameResidual *> &res, const std::vector<double> &H,
+                                            const std::vector<double> &b) {
     const int n = 8 * nFrames + CPARS;
-    std::vector<double> H((size_t)n * n), b(n);
-    if (ldso_ba_load_marginalization(margCtx_, ctx_, 0, &w) ||
-        ldso_ba_marginalize_points(margCtx_, adHTdeltaF.data(), H.data(), b.data())) {
-        fail("ldso_ba_marginalize_points");
-        return;
-    }
-    if (!read_residuals(margCtx_, pk.res)) {
-        fail("ldso_ba_get_residuals (marginalisation)");
-        return;
-    }
     passes_++;
     int nres = 0;
-    for (PointFrameResidual *r : pk.res) {
+    for (PointFrameResidual *r : res) {
         if (r->isActive()) {
             r->isLinearized = true;  // fixLinearizationF
             connectivityMap[conn_key(*r)][1]++;
@@ -502,6 +523,97 @@ void EnergyFunctional::marginalizePointsF() {
     }
     for (const shared_ptr<PointHessian> &p : allPointsToMarg) removePoint(p);
     makeIDX();
+}
+
+// marginalizePointsF from the loaded window's device arrays (setDeviceMarginalization).  Returns false
+// where that cannot give what the host path gives; true once the call is served (or failed: ok()).
+bool EnergyFunctional::marginalizeFromDevice() {
+    if (!ctx_ || !incremental_ || !resident_ || !mirrorTracked_ || resSync_ == ResSync::HostNewer) return false;
+    if ((int)loadedIds_.size() != nFrames) return false;
+    for (int f = 0; f < nFrames; f++)
+        if (loadedIds_[f] != frames[f]->frameID) return false;  // the loaded window has other frames
+    // current frame terms; without a structural change pending also the host's point values and residual edits
+    if (dirty_ ? !uploadFrameTerms() : !upload()) return true;
+    if (resSync_ == ResSync::HostNewer) return false;
+    const int R = (int)resPtr_.size();
+    std::vector<int32_t> pts;
+    std::vector<uint8_t> live((size_t)R, 0);
+    std::vector<PointFrameResidual *> res;
+    for (const shared_ptr<PointHessian> &p : allPointsToMarg) {
+        const auto it = mirrorPoint_.find(p.get());
+        if (it == mirrorPoint_.end() || (size_t)it->second >= ptPtr_.size() || ptPtr_[it->second] != p.get()) return false;
+        const int q = it->second;
+        const float pv[4] = {p->idepth_scaled, p->idepth_zero_scaled, p->priorF, p->deltaF};
+        if (std::memcmp(pv, &pointVals_[4 * (size_t)q], sizeof(pv)) != 0) return false;  // the device holds older values
+        int last = resBegin_[q] - 1;
+        for (const shared_ptr<PointFrameResidual> &r : p->residuals) {  // the loaded ones, in the loaded order
+            const int m = r->mirrorIdx;
+            if (m <= last || m >= resBegin_[q + 1] || resPtr_[m] != r.get()) return false;
+            live[m] = 1;
+            res.push_back(r.get());
+            last = m;
+        }
+        pts.push_back(q);
+    }
+    if (!margCtx_ && ldso_ba_create(device_, &margCtx_)) {
+        margCtx_ = nullptr;
+        fail("ldso_ba_create (marginalisation)");
+        return true;
+    }
+    ldso_ba_window w;
+    frameTermsWindow(w);
+    if (ldso_ba_load_marginalization_device(margCtx_, ctx_, 0, &w, (int32_t)pts.size(), pts.data(), live.data()))
+        return false;  // refused (ldso_ba_last_error says why): the host path
+    const int n = 8 * nFrames + CPARS;
+    std::vector<double> H((size_t)n * n), b(n);
+    if (ldso_ba_marginalize_points(margCtx_, adHTdeltaF.data(), H.data(), b.data())) {
+        fail("ldso_ba_marginalize_points");
+        return true;
+    }
+    if (!read_residuals(margCtx_, res)) {
+        fail("ldso_ba_get_residuals (marginalisation)");
+        return true;
+    }
+    deviceMargs_++;
+    applyMarginalization(res, H, b);
+    return true;
+}
+
+// EnergyFunctional.cc:205-262 with FullSystem.cc:1384-1404 (see the header)
+void EnergyFunctional::marginalizePointsF() {
+    epoch_++;
+    allPointsToMarg.clear();
+    for (const shared_ptr<PointHessian> &p : registry_)
+        if (p->status == PointStatus::MARGINALIZED && !p->alreadyRemoved) allPointsToMarg.push_back(p);
+    if (deviceMarg_ && (allPointsToMarg.empty() || marginalizeFromDevice())) return;
+    residualTouched();
+    if (allPointsToMarg.empty()) return;
+    if (!upload()) return;  // current frame terms; the parent window lends its device images
+    if (!margCtx_ && ldso_ba_create(device_, &margCtx_)) {
+        margCtx_ = nullptr;
+        fail("ldso_ba_create (marginalisation)");
+        return;
+    }
+    // the parent window as loaded holds every point still flagged ACTIVE before this call
+    std::vector<PointHessian *> pts;
+    for (const shared_ptr<PointHessian> &p : allPointsToMarg) pts.push_back(p.get());
+    PointPack pk;
+    pk.build(pts);
+    ldso_ba_window w;
+    frameTermsWindow(w);
+    pk.into(w);
+    const int n = 8 * nFrames + CPARS;
+    std::vector<double> H((size_t)n * n), b(n);
+    if (ldso_ba_load_marginalization(margCtx_, ctx_, 0, &w) ||
+        ldso_ba_marginalize_points(margCtx_, adHTdeltaF.data(), H.data(), b.data())) {
+        fail("ldso_ba_marginalize_points");
+        return;
+    }
+    if (!read_residuals(margCtx_, pk.res)) {
+        fail("ldso_ba_get_residuals (marginalisation)");
+        return;
+    }
+    applyMarginalization(pk.res, H, b);
 }
 
 // EnergyFunctional.cc:264-278
@@ -1082,6 +1194,7 @@ void EnergyFunctional::syncResiduals() {
     resSync_ = ResSync::Synced;  // before the reads: the residual setters called below see it synced
     deferred_ = false;
     const auto t0 = std::chrono::steady_clock::now();
+    readBacks_++;
     readBack(true);
     split_[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }

@@ -33,6 +33,19 @@
 //                   cycle's structural uploads spend their host time (EnergyFunctional::uploadSplit and
 //                   ldso_ba_edit_stats, ms per cycle); device: a further incremental run with kernel
 //                   timing on, whose HIP events bracket the edit's staging launches and k_edit_gather
+//   keyframe_cycle_close  only with `ldso_face_bench REPS --close`: the resident incremental cycle
+//                   extended by the keyframe's close (FullSystem.cc:606-634): after optimize(6) and
+//                   linearizeAll(true), removeOutliers' and flagPointsForRemoval's decision (a tenth of
+//                   the points, another tenth each cycle, is put out of bounds through its
+//                   lastResiduals; the threshold on idepth_hessian is their median, so half of them is
+//                   MARGINALIZED and half OUT), dropResidual of the inactive residuals, dropPointsF,
+//                   marginalizePointsF, marginalizeFrame, and as many new points activated as left.
+//                   With the device path off the decision is taken on the objects after the residual
+//                   read-back and marginalizePointsF packs its window from them; with it on
+//                   (flagPoints, setDeviceMarginalization) both stay on the device.  Alternated A B A B
+//                   in this process, each run with its own warm-up, the timed cycles pooled (median,
+//                   min, max); split: host clock per cycle of the decision, of marginalizePointsF, of
+//                   the read-backs (uploadSplit) and of the edit calls
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -59,6 +72,7 @@ int main(int argc, char **argv) {
     const int N = 7, P = 2000, W = 640, H = 480, n_its = 6;
     const int reps = argc > 1 ? std::atoi(argv[1]) : 10;
     const bool with_incremental = argc > 2 && std::strcmp(argv[2], "--incremental") == 0;
+    const bool with_close = argc > 2 && std::strcmp(argv[2], "--close") == 0;
     const int R = P * (N - 1);
     std::vector<ldso_ba_frame_state> fs(N);
     std::vector<float> dI((size_t)N * W * H * 3), th(N), pd((size_t)P * LDSO_BA_POINT_STRIDE), re(R);
@@ -561,6 +575,244 @@ int main(int argc, char **argv) {
                       ev.lib[0], ev.lib[4] / ne, ev.lib[5] / ne);
         kc_inc_json = buf;
     }
+    // --close: the resident incremental cycle with the keyframe's close, device path off and on
+    std::string kc_close_json;
+    if (with_close) {
+        struct CloseResult {
+            bool ok = false;
+            std::vector<double> ms;
+            double flag_ms = 0, marg_ms = 0, split[6] = {0, 0, 0, 0, 0, 0};
+            long read_backs = 0, device_margs = 0, edits = 0, fallen = 0;
+            long left[4] = {0, 0, 0, 0};  // points per status over the timed cycles
+            int cycles = 0;
+        };
+        // every run starts from the same calibration (optimize steps it), so that the two paths see the
+        // same windows and their point counts can be compared
+        const CalibHessian calib0 = *HCalib;
+        auto close_cycle = [&](bool device) {
+            CloseResult out;
+            auto HC = std::make_shared<CalibHessian>(calib0);
+            auto e2 = std::make_shared<EnergyFunctional>(0);
+            if (!e2->ok()) return out;
+            e2->setIncrementalEdits(true);
+            e2->setDeviceMarginalization(device);
+            auto new_frame = [&](int f, int id) {
+                auto F = std::make_shared<FrameHessian>();
+                F->frameID = id;
+                std::memcpy(F->worldToCam_evalPT, fs[f].world_to_cam_evalpt, sizeof(F->worldToCam_evalPT));
+                std::memcpy(F->state, fs[f].state, sizeof(F->state));
+                std::memcpy(F->state_zero, fs[f].state_zero, sizeof(F->state_zero));
+                F->ab_exposure = fs[f].ab_exposure;
+                F->dI = &dI[(size_t)f * W * H * 3];
+                F->frameEnergyTH = th[f];
+                return F;
+            };
+            std::vector<shared_ptr<FrameHessian>> fr;
+            for (int f = 0; f < N - 1; f++) {
+                fr.push_back(new_frame(f, f));
+                e2->insertFrame(fr.back(), HC);
+            }
+            // a point of the synthetic window enters (at the start, and again after it left): `user`
+            // keeps its index there
+            std::vector<intptr_t> src_of;
+            auto activate = [&](int p) {
+                auto Pt = std::make_shared<PointHessian>();
+                const float *d = &pd[(size_t)p * LDSO_BA_POINT_STRIDE];
+                Pt->host = fr[ph[p]];
+                Pt->u = d[0];
+                Pt->v = d[1];
+                Pt->setIdepth(d[2]);
+                Pt->setIdepthZero(d[3]);
+                std::memcpy(Pt->color, d + 8, sizeof(Pt->color));
+                std::memcpy(Pt->weights, d + 16, sizeof(Pt->weights));
+                Pt->user = reinterpret_cast<void *>((intptr_t)p);
+                for (int k = rb[p]; k < rb[p + 1]; k++) {
+                    if (rt[k] == N - 1) continue;
+                    auto r = std::make_shared<PointFrameResidual>(Pt, fr[ph[p]], fr[rt[k]]);
+                    r->isNew = true;
+                    Pt->residuals.push_back(r);
+                }
+                e2->insertPoint(Pt);
+                for (auto &r : Pt->residuals) e2->insertResidual(r);
+            };
+            for (int p = 0; p < P; p++)
+                if (ph[p] != N - 1) activate(p);
+            e2->makeIDX();
+            ldso_ba_flag_params fpar;
+            ldso_ba_default_flag_params(&fpar);
+            const int warm = 2;
+            double split0[6] = {0, 0, 0, 0, 0, 0};
+            long rb0 = 0;
+            for (int c = 0; c < warm + reps && e2->ok(); c++) {
+                if (c == warm) {
+                    std::memcpy(split0, e2->uploadSplit(), sizeof(split0));
+                    rb0 = e2->residualReadBacks();
+                }
+                auto F = new_frame(N - 1, 100 + c);
+                auto t1 = Clock::now();
+                e2->insertFrame(F, HC);
+                for (auto &Pt : std::vector<shared_ptr<PointHessian>>(e2->allPoints)) {
+                    auto r = std::make_shared<PointFrameResidual>(Pt, Pt->host.lock(), F);
+                    r->isNew = true;
+                    Pt->residuals.push_back(r);
+                    e2->insertResidual(r);
+                }
+                e2->makeIDX();
+                e2->setAdjointsF(HC);
+                e2->setDeltaF(HC);
+                e2->optimize(n_its, HC, nullptr, nullptr, nullptr, &all_its);
+                e2->setAdjointsF(HC);
+                e2->setDeltaF(HC);
+                e2->linearizeAll(true);
+                // the frontend's bookkeeping, allPoints order (untimed share: the same on both paths)
+                const std::vector<shared_ptr<PointHessian>> pts = e2->allPoints;
+                const int Pn = (int)pts.size(), Nn = e2->nFrames;
+                std::vector<int32_t> numGood(Pn, 10), lastRes(2 * (size_t)Pn, -1);
+                std::vector<int8_t> lastState(2 * (size_t)Pn, (int8_t)IN);
+                std::vector<PointFrameResidual *> lastPtr(2 * (size_t)Pn, nullptr);
+                std::vector<float> ih;
+                for (int q = 0; q < Pn; q++) {
+                    if ((q + c) % 10 == 0) {  // its lastResiduals[0] left the window OOB
+                        lastState[2 * (size_t)q] = (int8_t)OOB;
+                        ih.push_back(pts[q]->idepth_hessian);
+                        continue;
+                    }
+                    for (auto &r : pts[q]->residuals) {
+                        const int t = r->target.lock()->idx;
+                        if (t >= Nn - 2) {
+                            lastPtr[2 * (size_t)q + (Nn - 1 - t)] = r.get();
+                            lastRes[2 * (size_t)q + (Nn - 1 - t)] = r->mirrorIdx;
+                        }
+                    }
+                }
+                std::sort(ih.begin(), ih.end());
+                fpar.min_idepth_h_marg = ih.empty() ? 50.0f : ih[ih.size() / 2];
+                auto t2 = Clock::now();
+                std::vector<PointFrameResidual *> toRemove;
+                long left[4] = {0, 0, 0, 0};
+                if (device) {
+                    const EnergyFunctional::FlagResult fx = e2->flagPoints(&fpar, {}, numGood, lastRes, lastState);
+                    if (!fx.ok) break;
+                    toRemove = fx.toRemove;
+                    for (int i = 0; i < 4; i++) left[i] = fx.counts[i];
+                } else {
+                    e2->syncResiduals();
+                    const int A = fpar.min_good_active_res_for_marg, G = fpar.min_good_res_for_marg;
+                    for (int q = 0; q < Pn; q++) {
+                        PointHessian &pt = *pts[q];
+                        int n_live = 0, vis = 0;
+                        for (auto &r : pt.residuals) {
+                            if (!r->isActive()) {
+                                toRemove.push_back(r.get());
+                                continue;
+                            }
+                            n_live++;
+                            if (r->state_state == IN && r->target.lock()->flaggedForMarginalization) vis++;
+                        }
+                        int8_t ls[2];
+                        for (int i = 0; i < 2; i++)
+                            ls[i] = lastPtr[2 * (size_t)q + i] ? (int8_t)lastPtr[2 * (size_t)q + i]->state_state : lastState[2 * (size_t)q + i];
+                        const int ng = numGood[q] + n_live;
+                        int st = LDSO_BA_PT_ACTIVE;
+                        if (pt.idepth_scaled < 0 || n_live == 0) {
+                            st = LDSO_BA_PT_OUTLIER;
+                        } else {
+                            const bool oob = (n_live >= A && ng > G + 10 && n_live - vis < A) || ls[0] == OOB ||
+                                             (n_live >= 2 && ls[0] == OUTLIER && ls[1] == OUTLIER);
+                            if (oob || pt.host.lock()->flaggedForMarginalization)
+                                st = n_live >= A && ng >= G && pt.idepth_hessian > fpar.min_idepth_h_marg ? LDSO_BA_PT_MARGINALIZED
+                                                                                                         : LDSO_BA_PT_OUT;
+                        }
+                        pt.status = (PointStatus)st;
+                        left[st]++;
+                    }
+                }
+                const double flag_ms = ms_since(t2);
+                for (PointFrameResidual *r : toRemove) {
+                    auto pt = r->point.lock();
+                    for (auto &x : pt->residuals)
+                        if (x.get() == r) {
+                            e2->dropResidual(x);
+                            break;
+                        }
+                }
+                std::vector<int> back;
+                for (auto &pt : pts)
+                    if (pt->status != PointStatus::ACTIVE) back.push_back((int)reinterpret_cast<intptr_t>(pt->user));
+                e2->dropPointsF();
+                auto t3 = Clock::now();
+                e2->marginalizePointsF();
+                const double marg_ms = ms_since(t3);
+                for (auto &pt : std::vector<shared_ptr<PointHessian>>(e2->allPoints)) {
+                    const auto rs = pt->residuals;
+                    for (auto &r : rs)
+                        if (r->target.lock() == F) e2->dropResidual(r);
+                }
+                e2->marginalizeFrame(F);
+                for (int p : back) activate(p);
+                e2->makeIDX();
+                if (c >= warm) {
+                    out.ms.push_back(ms_since(t1));
+                    out.flag_ms += flag_ms;
+                    out.marg_ms += marg_ms;
+                    for (int i = 0; i < 4; i++) out.left[i] += left[i];
+                }
+            }
+            if (!e2->ok() || out.ms.empty()) {
+                std::fprintf(stderr, "keyframe_cycle_close: %s\n", e2->lastError().c_str());
+                return out;
+            }
+            out.cycles = (int)out.ms.size();
+            for (int i = 0; i < 6; i++) out.split[i] = e2->uploadSplit()[i] - split0[i];
+            out.read_backs = e2->residualReadBacks() - rb0;
+            out.device_margs = e2->deviceMarginalizations();
+            out.edits = e2->editsApplied();
+            out.fallen = e2->editsFallenBack();
+            out.ok = true;
+            return out;
+        };
+        auto pool = [](CloseResult a, const CloseResult &b) {
+            a.ok = a.ok && b.ok;
+            a.ms.insert(a.ms.end(), b.ms.begin(), b.ms.end());
+            a.flag_ms += b.flag_ms;
+            a.marg_ms += b.marg_ms;
+            a.read_backs += b.read_backs;
+            a.device_margs += b.device_margs;
+            a.edits += b.edits;
+            a.fallen += b.fallen;
+            a.cycles += b.cycles;
+            for (int i = 0; i < 6; i++) a.split[i] += b.split[i];
+            for (int i = 0; i < 4; i++) a.left[i] += b.left[i];
+            return a;
+        };
+        const CloseResult h1 = close_cycle(false), d1 = close_cycle(true), h2 = close_cycle(false), d2 = close_cycle(true);
+        auto close_json = [](CloseResult c) {
+            char b[1024];
+            const double n = c.cycles > 0 ? c.cycles : 1;
+            double med = -1, lo = -1, hi = -1;
+            if (c.ok && !c.ms.empty()) {
+                std::sort(c.ms.begin(), c.ms.end());
+                med = c.ms[c.ms.size() / 2];
+                lo = c.ms.front();
+                hi = c.ms.back();
+            }
+            std::snprintf(b, sizeof(b),
+                          "{\"ok\": %s, \"ms_median\": %.6f, \"ms_min\": %.6f, \"ms_max\": %.6f, \"cycles\": %d, "
+                          "\"residual_read_backs_per_cycle\": %.3f, \"device_marginalizations\": %ld, \"edits_applied\": %ld, "
+                          "\"edits_fallen_back\": %ld, \"points_per_cycle\": {\"active\": %.1f, \"outlier\": %.1f, \"out\": %.1f, "
+                          "\"marginalized\": %.1f}, \"split\": {\"decision_ms\": %.4f, \"marginalize_points_ms\": %.4f, "
+                          "\"read_back_ms\": %.4f, \"structural_uploads\": %.2f, \"edit_or_reload_call_ms\": %.4f}}",
+                          c.ok ? "true" : "false", med, lo, hi, c.cycles, c.read_backs / n, c.device_margs, c.edits, c.fallen,
+                          c.left[0] / n, c.left[1] / n, c.left[2] / n, c.left[3] / n, c.flag_ms / n, c.marg_ms / n, c.split[1] / n,
+                          c.split[0] / n, c.split[4] / n);
+            return std::string(b);
+        };
+        kc_close_json = ", \"keyframe_cycle_close\": {\"what\": \"the resident incremental keyframe_cycle with linearizeAll(true) and "
+                        "the keyframe's close (decision, dropResidual, dropPointsF, marginalizePointsF, marginalizeFrame, "
+                        "re-activation), device path off / on, alternated in one process, 2 x " + std::to_string(reps) +
+                        " cycles each; host clock; the decision's time includes the host path's residual read-back\", "
+                        "\"host\": " + close_json(pool(h1, h2)) + ", \"device\": " + close_json(pool(d1, d2)) + "}";
+    }
     // one device-to-device ingest of the tracker's new frame (event record / wait, the layout-3
     // kernel): back to back on the host clock, one synchronisation at the end
     double ingest_us = -1;
@@ -611,10 +863,10 @@ int main(int argc, char **argv) {
         "with the residual / point write-back\"}, "
         "\"c_abi_optimize\": {\"ms_per_optimize\": %.6f, \"ms_per_gn_iteration\": %.6f}, "
         "\"flag_loop\": {\"residuals\": %d, \"ms\": %.6f, \"device_passes\": %ld}, "
-        "\"keyframe_cycle\": %s%s}\n",
+        "\"keyframe_cycle\": %s%s%s}\n",
         n_its, reps, ok ? "true" : "false", ms_opt, ms_opt / n_its, n_its, its_default, (int)vr.size(), (int)ef->allPoints.size(),
         ms_shim_digest, ms_shim_vec, ms_shim_map, ms_shim_digest / n_its, ms_shim_digest / ms_opt, ms_shim_vec / ms_opt,
         toRemove.size(),
-        ms_full, ms_raw, ms_raw / n_its, nres, ms_flag, flag_passes, kc_json.c_str(), kc_inc_json.c_str());
+        ms_full, ms_raw, ms_raw / n_its, nres, ms_flag, flag_passes, kc_json.c_str(), kc_inc_json.c_str(), kc_close_json.c_str());
     return ok ? 0 : 1;
 }

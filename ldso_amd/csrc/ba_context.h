@@ -13,6 +13,7 @@
 #include "../../include/ldso_ba.h"
 #include "../../include/ldso_ct.h"
 #include "ba_device.h"
+#include "edit_plan.h"
 #include "hip_owning.h"
 
 namespace {
@@ -223,6 +224,16 @@ struct ldso_ba_ctx {
     double ed_stat[6] = {0, 0, 0, 0, 0, 0};
     Event ed_ev[3];
     bool ed_ev_pending = false;
+    // ldso_ba_flag_points: one device block and one pinned block for the call's upload and download
+    // (grow-only), and the loaded window's caller-order maps (flag_map_win: the window they were read
+    // for, -1 after every load or edit).  d_flag is in no captured graph: a plain DevBuf, so that its
+    // growth makes no context capture its graphs again
+    DevBuf<int> d_flag;
+    PinBuf<int> pin_flag;
+    ldso_ba::OldWindow flag_map;
+    int flag_map_win = -1;
+    // ldso_ba_load_marginalization_device, on the marginalisation context: parent -> gather, gather -> parent
+    Event mg_ev_a, mg_ev_b;
     int64_t xfer[4] = {0, 0, 0, 0};  // ldso_ba_transfer_stats
     // timing-only events: no system-scope fence (its L2 write-back and invalidate would be timed, and
     // would slow the kernel after the start event)

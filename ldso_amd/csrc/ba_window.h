@@ -2,6 +2,8 @@
 // buffers a Layout sizes; ldso_ba_load* (load_impl: every buffer allocated anew and uploaded) and
 // ldso_ba_edit_window (edit_impl: grown where too small, the carried arrays gathered on the device)
 // each walk it once, so that an edited context is a fresh load of the same window by construction.
+// ldso_ba_load_marginalization_device is load_impl's walk with the carried arrays sized instead of
+// uploaded and k_edit_gather pointed at the parent's arrays (marg_gather).
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -13,6 +15,7 @@
 #include "edit_plan.h"
 #include "k_edit.h"
 #include "layout.h"
+#include "marg_plan.h"
 
 namespace {
 
@@ -105,6 +108,9 @@ struct WindowWalk {
     int rc = 0;
     InBatch ups;     // the host arrays: a load copies each on the stream, an edit flushes the batch
     EditParams E{};  // fill_*, and state_NewState as newstate [R]
+    // a load whose carried arrays are gathered on the device (ldso_ba_load_marginalization_device):
+    // they are sized and not uploaded
+    bool gather_carried = false;
     template <typename T>
     void sized(GraphBuf<T> &buf, size_t count) {
         if (!rc) rc = kEdit ? edit_grow(c, buf, count) : buf.alloc(std::max<size_t>(1, count));
@@ -119,6 +125,7 @@ struct WindowWalk {
     template <typename T, typename V>
     void carried(GraphBuf<T> &buf, GraphBuf<T> &other, std::vector<V> &v) {
         if (kEdit) sized(other, v.size());
+        else if (gather_carried) sized(buf, v.size());
         else host(buf, v, v.size());
     }
     // a fill covers the count and not the allocation: they differ by the one dummy element of an
@@ -181,6 +188,7 @@ void adopt_layout(ldso_ba_ctx *c, Layout &L, int n_windows) {
     c->n_sum_blocks = (int)L.sum_blocks.size();
     c->ns_cache.clear();
     c->ns_cache_null = -1;
+    c->flag_map_win = -1;
 }
 
 // k_point_sc's dynamic LDS where the widest loaded window needs more than the default limit
@@ -226,20 +234,71 @@ int place_store_frames(ldso_ba_ctx *c, const std::vector<int> &fslot) {
     return 0;
 }
 
+// ldso_ba_load_marginalization_device's gather, once the marginalisation context's buffers stand and
+// its gather indices (d_ed_rs_src, d_ed_pt_src: positions in the parent's window) are uploaded:
+// k_edit_gather with its sources at the parent's arrays, priorF scaled.  The two streams are ordered
+// by events and never by the host: the gather waits for what the parent's stream holds now, and
+// whatever that stream is given later -- a pass, an edit that swaps the arrays -- waits for the gather.
+// F: the load walk's parameters (newstate and R; its fills are load_apply's).
+int marg_gather(ldso_ba_ctx *c, const ldso_ba_ctx *parent, int parent_win, const EditParams &F) {
+    int rc;
+    if ((rc = c->mg_ev_a.ensure(hipEventDisableTiming)) || (rc = c->mg_ev_b.ensure(hipEventDisableTiming))) return rc;
+    const WinDev &pw = parent->wd[parent_win];
+    EditParams E = F;
+    E.n_fill = 0;
+    E.rs_src = c->d_ed_rs_src.p;
+    E.pt_src = c->d_ed_pt_src.p;
+    E.o_state = parent->d_rs_state.p + pw.res_base;
+    E.o_flags = parent->d_rs_flags.p + pw.res_base;
+    E.o_energy = parent->d_rs_energy.p + pw.res_base;
+    E.o_newenergy = E.o_energy;  // as a load: state_NewEnergy is loaded equal to state_energy
+    E.o_pt = reinterpret_cast<const float4 *>(parent->d_pt_data.p) + (size_t)pw.point_base * kPtVec;
+    E.n_state = nullptr;  // every index is a position of the parent (marg_plan.cpp): no new entries
+    E.n_flags = nullptr;
+    E.n_energy = nullptr;
+    E.n_pt = nullptr;
+    E.state = c->d_rs_state.p;
+    E.flags = c->d_rs_flags.p;
+    E.energy = c->d_rs_energy.p;
+    E.newenergy = c->d_rs_newenergy.p;
+    E.pt = reinterpret_cast<float4 *>(c->d_pt_data.p);
+    E.newstate = c->d_rs_newstate.p;
+    E.R = c->R_tot;
+    E.P = c->P_tot;
+    E.scale_prior = 1;
+    E.prior_fac = kIdepthFixPriorMargFac;
+    HIP_TRY(hipEventRecord(c->mg_ev_a.e, parent->stream));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->mg_ev_a.e, 0));
+    const size_t work = std::max<size_t>((size_t)E.R, (size_t)E.P * kPtVec);
+    if (work) {
+        const int nb = (int)std::min<size_t>(1024, (work + 255) / 256);
+        k_edit_gather<<<nb, 256, 0, c->stream>>>(E);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(c->mg_ev_b.e, c->stream));
+    HIP_TRY(hipStreamWaitEvent(parent->stream, c->mg_ev_b.e, 0));
+    return 0;
+}
+
 // parent != nullptr: a marginalisation context over `ws[0]` whose frames are the parent's window
 // parent_win (images borrowed, not uploaded; priorF scaled by setting_idepthFixPriorMargFac)
 // frame_ids != nullptr (ldso_ba_load_frames): the windows' frames are resident in the frame store
 // under these ids, [sum N]; the windows' dI is not read
+// gather != nullptr (ldso_ba_load_marginalization_device, with parent): the layout is the plan's, and
+// the carried arrays -- the point records and the residuals' state, energy and flags -- are gathered
+// from the parent's device arrays by k_edit_gather instead of uploaded; ws is not read
 int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32_t shard_rank, int32_t shard_count,
-              const ldso_ba_ctx *parent, int parent_win, const int64_t *frame_ids = nullptr) {
+              const ldso_ba_ctx *parent, int parent_win, const int64_t *frame_ids = nullptr, MargPlan *gather = nullptr) {
     if (!c || n_windows < 1 || !ws) return fail(-1, "bad arguments");
     if (shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return fail(-1, "bad shard");
     const FrameStore &S = c->store;
     if (frame_ids && S.cap == 0) return fail(LDSO_BA_ERR_FRAME_STORE, "no frame store: call ldso_ba_frames_reserve first");
-    Layout L;
-    int rc = build_layout(ws, n_windows, shard_rank, shard_count, c->item_order, c->top_chunk, parent != nullptr, L,
-                          frame_ids != nullptr);
+    Layout L_own;
+    int rc = gather ? 0
+                    : build_layout(ws, n_windows, shard_rank, shard_count, c->item_order, c->top_chunk, parent != nullptr, L_own,
+                                   frame_ids != nullptr);
     if (rc) return rc;
+    Layout &L = gather ? gather->L : L_own;
     std::vector<int> fslot;
     if (frame_ids && (rc = store_slots(S, ws, n_windows, frame_ids, fslot))) return rc;
     HIP_TRY(hipSetDevice(c->device));
@@ -269,8 +328,18 @@ int load_impl(ldso_ba_ctx *c, int32_t n_windows, const ldso_ba_window *ws, int32
         c->xfer[2]++;
         c->img_tag.clear();
     }
+    if (gather) {  // the gather indices travel with the load's uploads
+        A.gather_carried = true;
+        A.sized(c->d_ed_rs_src, gather->rs_gather.size());
+        A.sized(c->d_ed_pt_src, gather->pt_gather.size());
+        if (!A.rc) {
+            A.ups.add(c->d_ed_rs_src.p, gather->rs_gather.data(), gather->rs_gather.size() * sizeof(int));
+            A.ups.add(c->d_ed_pt_src.p, gather->pt_gather.data(), gather->pt_gather.size() * sizeof(int));
+        }
+    }
     window_buffers(c, L, (size_t)n_windows, A);
     if ((rc = load_apply(c, A))) return rc;
+    if (gather && (rc = marg_gather(c, parent, parent_win, A.E))) return rc;
     // images: per frame through a float3 staging buffer, repacked on the device; the
     // intensity-only layout falls back to 2x4 float4 tiles if the caller's gradients are not
     // makeImages' (then recomputing them would not be exact)

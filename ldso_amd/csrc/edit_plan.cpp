@@ -6,14 +6,6 @@
 
 namespace ldso_ba {
 
-namespace {
-// the loaded window's structure in caller order, read back from what build_layout left
-struct OldWindow {
-    int N = 0, P = 0, R = 0;
-    std::vector<int> pt_pos, rs_pos;          // caller index -> device position
-    std::vector<int> pt_host;                 // caller point -> host frame
-    std::vector<int> rs_point, rs_target;     // caller residual -> caller point, target frame
-};
 void read_old(const WinHost &H, const WinDesc &D, OldWindow &o) {
     o.N = H.N;
     o.P = H.P;
@@ -37,6 +29,8 @@ void read_old(const WinHost &H, const WinDesc &D, OldWindow &o) {
         o.rs_target[k] = s < h ? s : s + 1;
     }
 }
+
+namespace {
 // every src in [-1, n_old), no old index twice; counts the new entries
 int check_src(const int32_t *src, int n, int n_old, const char *what, std::vector<int> &fresh) {
     std::vector<char> used(n_old, 0);
@@ -158,7 +152,7 @@ void copy_out(int32_t *dst, const std::vector<T> &v) {
     if (dst)
         for (size_t i = 0; i < v.size(); i++) dst[i] = (int32_t)v[i];
 }
-// the descriptor's integer fields and bases (the float fields follow from `after` alone)
+// the descriptor's integer fields and bases (the float fields follow from the window's frame terms alone)
 bool same_desc(const WinDesc &a, const WinDesc &b) {
     return a.N == b.N && a.P == b.P && a.R == b.R && a.D == b.D && a.frame_base == b.frame_base && a.pair_base == b.pair_base &&
            a.point_base == b.point_base && a.res_base == b.res_base && a.top_item_base == b.top_item_base &&
@@ -169,6 +163,24 @@ bool same_desc(const WinDesc &a, const WinDesc &b) {
            a.height == b.height;
 }
 }  // namespace
+
+int ldso_ba::layout_index_mismatches(const Layout &L, const Layout &A) {
+    const bool same[] = {same_bytes(L.top_items, A.top_items), same_bytes(L.sc_items, A.sc_items),
+                         same_bytes(L.pair_items, A.pair_items), same_bytes(L.host_items, A.host_items),
+                         same_bytes(L.sum_blocks, A.sum_blocks), same_bytes(L.pair_win, A.pair_win),
+                         same_bytes(L.frame_win, A.frame_win), same_bytes(L.pt_win, A.pt_win),
+                         same_bytes(L.rs_slot, A.rs_slot), same_bytes(L.pt_nres, A.pt_nres),
+                         same_bytes(L.pt_host, A.pt_host), same_bytes(L.pt_tgt, A.pt_tgt),
+                         same_bytes(L.rs_tgt, A.rs_tgt), same_bytes(L.wh[0].rs_orig, A.wh[0].rs_orig),
+                         same_bytes(L.wh[0].pt_orig, A.wh[0].pt_orig), same_bytes(L.wh[0].rs_slot, A.wh[0].rs_slot),
+                         same_desc(L.wd[0], A.wd[0]),
+                         L.sc_slab_total == A.sc_slab_total && L.sys_total == A.sys_total &&
+                             L.stage_total == A.stage_total && L.vec_total == A.vec_total && L.rec_base == A.rec_base &&
+                             L.chunk == A.chunk && L.sc_chunk == A.sc_chunk && L.smem_max == A.smem_max};
+    int bad = 0;
+    for (bool s : same) bad += s ? 0 : 1;
+    return bad;
+}
 
 extern "C" int ldso_ba_edit_plan_check(const ldso_ba_window *before, const ldso_ba_edit *e, int32_t item_order,
                                        int32_t top_chunk, int32_t *res_gather, int32_t *point_gather,
@@ -189,22 +201,7 @@ extern "C" int ldso_ba_edit_plan_check(const ldso_ba_window *before, const ldso_
     if (n_mismatch) {
         Layout A;
         if ((rc = build_layout(e->after, 1, 0, 1, item_order, top_chunk, false, A, true))) return rc;
-        const Layout &L = plan.L;
-        const bool same[] = {same_bytes(L.top_items, A.top_items), same_bytes(L.sc_items, A.sc_items),
-                             same_bytes(L.pair_items, A.pair_items), same_bytes(L.host_items, A.host_items),
-                             same_bytes(L.sum_blocks, A.sum_blocks), same_bytes(L.pair_win, A.pair_win),
-                             same_bytes(L.frame_win, A.frame_win), same_bytes(L.pt_win, A.pt_win),
-                             same_bytes(L.rs_slot, A.rs_slot), same_bytes(L.pt_nres, A.pt_nres),
-                             same_bytes(L.pt_host, A.pt_host), same_bytes(L.pt_tgt, A.pt_tgt),
-                             same_bytes(L.rs_tgt, A.rs_tgt), same_bytes(L.wh[0].rs_orig, A.wh[0].rs_orig),
-                             same_bytes(L.wh[0].pt_orig, A.wh[0].pt_orig), same_bytes(L.wh[0].rs_slot, A.wh[0].rs_slot),
-                             same_desc(L.wd[0], A.wd[0]),
-                             L.sc_slab_total == A.sc_slab_total && L.sys_total == A.sys_total &&
-                                 L.stage_total == A.stage_total && L.vec_total == A.vec_total && L.rec_base == A.rec_base &&
-                                 L.chunk == A.chunk && L.sc_chunk == A.sc_chunk && L.smem_max == A.smem_max};
-        int bad = 0;
-        for (bool s : same) bad += s ? 0 : 1;
-        *n_mismatch = bad;
+        *n_mismatch = layout_index_mismatches(plan.L, A);
     }
     return 0;
 }

@@ -9,6 +9,20 @@
 
 namespace ldso_ba {
 
+// A loaded (unsharded) window's structure in caller order, read back from what build_layout left:
+// what the planners and ldso_ba_flag_points translate the caller's indices with.
+struct OldWindow {
+    int N = 0, P = 0, R = 0;
+    std::vector<int> pt_pos, rs_pos;       // caller index -> device position
+    std::vector<int> pt_host;              // caller point -> host frame
+    std::vector<int> rs_point, rs_target;  // caller residual -> caller point, target frame
+};
+void read_old(const WinHost &H, const WinDesc &D, OldWindow &o);
+// The planners' self-check (ldso_ba_edit_plan_check, ldso_ba_marg_plan_check): the number of index
+// arrays (work items, record slots, target lists, counts, the descriptor's bases, device orders,
+// totals) in which two single-window layouts differ.
+int layout_index_mismatches(const Layout &L, const Layout &A);
+
 struct EditPlan {
     // build_layout(after) with item order 0 or 1: every index array is the one a fresh load of the
     // edited window uploads.  Its value arrays (rs_state, rs_energy, rs_flags, pt_data) hold the

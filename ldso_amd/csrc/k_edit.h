@@ -31,6 +31,10 @@ struct EditParams {
     long long fill_words[kEditFills];
     unsigned fill_val[kEditFills];
     int n_fill;
+    // ldso_ba_load_marginalization_device (the sources are the parent's arrays): priorF, float 4 of
+    // every gathered record, times setting_idepthFixPriorMargFac (layout.cpp's marg load); 0 = an edit
+    int scale_prior;
+    float prior_fac;
 };
 constexpr int kPtVec = LDSO_BA_POINT_STRIDE / 4;
 
@@ -64,7 +68,9 @@ __global__ __launch_bounds__(256) void k_edit_gather(EditParams E) {
     }
     for (int i = tid; i < kPtVec * E.P; i += nth) {
         const int q = i / kPtVec, k = i - kPtVec * q, s = pt_src[q];
-        E.pt[i] = s >= 0 ? E.o_pt[(size_t)s * kPtVec + k] : E.n_pt[(size_t)(~s) * kPtVec + k];
+        float4 v = s >= 0 ? E.o_pt[(size_t)s * kPtVec + k] : E.n_pt[(size_t)(~s) * kPtVec + k];
+        if (E.scale_prior && k == 1) v.x *= E.prior_fac;
+        E.pt[i] = v;
     }
     for (int f = 0; f < E.n_fill; f++) {
         unsigned *dst = E.fill_dst[f];

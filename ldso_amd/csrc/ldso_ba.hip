@@ -43,8 +43,9 @@
 //                     AccumulatorApprox block; a template, so its instantiations are emitted after every
 //                     other kernel wherever it is defined
 //   k_point_sc.h, k_stitch.h, k_stitch_host.h, k_solve.h, k_solve_reg.h, k_solve_fast.h, k_exchange.h,
-//   k_xad.h, k_activate.h, k_resubstitute.h, k_step.h, k_io.h, k_edit.h (ldso_ba_edit_window's gather)
-//                     the 26 non-template kernels by stage, included below in the order the kernels have
+//   k_xad.h, k_activate.h, k_resubstitute.h, k_step.h, k_io.h, k_edit.h (ldso_ba_edit_window's gather,
+//   which ldso_ba_load_marginalization_device points at the parent's arrays), k_flag.h (ldso_ba_flag_points)
+//                     the 28 non-template kernels by stage, included below in the order the kernels have
 //                     always been defined in
 //   hip_owning.h      shared with ldso_ct.hip: fail / HIP_TRY, the owning buffers and events, KernelTimer
 //   ba_context.h      the timing slots, the environment switches (read_switches), the allocation
@@ -91,7 +92,9 @@
 #include "k_step.h"
 #include "k_io.h"
 #include "k_edit.h"
+#include "k_flag.h"
 #include "edit_plan.h"
+#include "marg_plan.h"
 #include "ba_context.h"
 #include "ba_launch.h"
 #include "ba_window.h"
@@ -361,6 +364,132 @@ int ldso_ba_load_marginalization(ldso_ba_ctx *marg, const ldso_ba_ctx *parent, i
         return fail(-1, "marginalisation window does not match the parent window's frames");
     marg->settings = parent->settings;  // the parent's affine modes shape res_toZeroF and Jab_r
     return load_impl(marg, 1, points, 0, 1, parent, parent_win);
+}
+
+int ldso_ba_load_marginalization_device(ldso_ba_ctx *marg, const ldso_ba_ctx *parent, int32_t parent_win,
+                                        const ldso_ba_window *frame_terms, int32_t n_points, const int32_t *points,
+                                        const uint8_t *res_live) {
+    if (!marg || !parent || !frame_terms || marg == parent) return fail(-1, "bad arguments");
+    if (parent_win < 0 || parent_win >= parent->n_win) return fail(-1, "parent window out of range");
+    if (marg->device != parent->device) return fail(-1, "contexts on different devices");
+    if (parent->marg) return fail(-1, "the parent is a marginalisation context");
+    if (parent->shard_count > 1 || parent->comm) return fail(-1, "marginalisation from the device: not from a sharded parent");
+    const WinDev &pw = parent->wd[parent_win];
+    if (frame_terms->n_frames != pw.N || frame_terms->width != pw.width || frame_terms->height != pw.height)
+        return fail(-1, "marginalisation window does not match the parent window's frames");
+    MargPlan plan;
+    int rc = plan_marg(parent->wh[parent_win], pw, *frame_terms, n_points, points, res_live, marg->item_order,
+                       marg->top_chunk, plan);
+    if (rc) return rc;
+    marg->settings = parent->settings;
+    return load_impl(marg, 1, frame_terms, 0, 1, parent, parent_win, nullptr, &plan);
+}
+
+void ldso_ba_default_flag_params(ldso_ba_flag_params *p) {
+    if (p) *p = ldso_ba_flag_params{3, 4, 50.0f, 0};  // Setting.cc: minGoodActiveResForMarg, minGoodResForMarg, minIdepthH_marg
+}
+
+int ldso_ba_flag_points(ldso_ba_ctx *c, int32_t win, const ldso_ba_flag_params *params, const uint8_t *frame_flagged,
+                        const int32_t *num_good, const int32_t *last_res, const int8_t *last_state, int8_t *status,
+                        uint8_t *res_live, int32_t *num_good_out, int8_t *last_state_out, int32_t *counts) {
+    if (!c || win < 0 || win >= c->n_win || !frame_flagged) return fail(-1, "bad arguments");
+    if (c->marg) return fail(-1, "flag_points: not on a marginalisation context");
+    if (c->shard_count > 1 || c->comm) return fail(-1, "flag_points: not on a sharded context");
+    const WinDev &D = c->wd[win];
+    const WinHost &H = c->wh[win];
+    const int P = D.P, R = D.R;
+    if (P > 0 && (!num_good || !last_res)) return fail(-1, "flag_points: null num_good or last_res");
+    ldso_ba_flag_params fp;
+    ldso_ba_default_flag_params(&fp);
+    if (params) fp = *params;
+    if (c->flag_map_win != win) {
+        read_old(H, D, c->flag_map);
+        c->flag_map_win = win;
+    }
+    const OldWindow &o = c->flag_map;
+    for (int i = 0; i < 2 * P; i++) {
+        const int k = last_res[i];
+        if (k == -1) {
+            if (!last_state) return fail(-1, "flag_points: last_res holds -1 and last_state is null");
+            continue;
+        }
+        if (k < 0 || k >= R || o.rs_point[k] != i / 2)
+            return fail(-1, "flag_points: last_res[" + std::to_string(i / 2) + "][" + std::to_string(i & 1) + "] = " +
+                                std::to_string(k) + " is neither -1 nor a residual of its point");
+    }
+    // one block of 32-bit words: [num_good P | last_res 2P | last_state 2P bytes | frame_flagged 16 bytes |
+    // cnt P (0) | counts 4 (0)] goes up, [counts 4 | num_good_out P | status P bytes | ls 2P bytes |
+    // res_live R bytes] comes back
+    const size_t w4 = sizeof(int);
+    const size_t o_ng = 0, o_lr = o_ng + P, o_ls = o_lr + 2 * (size_t)P, o_ff = o_ls + pad4(2 * (size_t)P) / w4,
+                 o_cnt = o_ff + LDSO_BA_MAX_FRAMES / w4, o_counts = o_cnt + P, o_ngo = o_counts + 4, o_st = o_ngo + P,
+                 o_lso = o_st + pad4(P) / w4, o_live = o_lso + pad4(2 * (size_t)P) / w4, n_words = o_live + pad4(R) / w4;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if (c->d_flag.n < n_words || c->pin_flag.n < n_words) {  // nothing of an earlier call is in flight: each ends synchronised
+        const size_t grow = std::max(n_words, c->d_flag.n + c->d_flag.n / 2);
+        if ((rc = c->d_flag.alloc(grow)) || (rc = c->pin_flag.ensure(grow))) return rc;
+    }
+    int *hp = c->pin_flag.p;
+    std::memset(hp, 0, (o_counts + 4) * w4);
+    int8_t *h_ls = reinterpret_cast<int8_t *>(hp + o_ls);
+    for (int q = 0; q < P; q++) {
+        const int p = H.pt_orig[q];
+        hp[o_ng + q] = num_good[p];
+        for (int i = 0; i < 2; i++) {
+            const int k = last_res[2 * p + i];
+            hp[o_lr + 2 * q + i] = k >= 0 ? o.rs_pos[k] : -1;
+            h_ls[2 * q + i] = k >= 0 ? 0 : last_state[2 * p + i];
+        }
+    }
+    std::memcpy(hp + o_ff, frame_flagged, (size_t)D.N);
+    int *dp = c->d_flag.p;
+    HIP_TRY(hipMemcpyAsync(dp, hp, (o_counts + 4) * w4, hipMemcpyHostToDevice, c->stream));
+    FlagParams F{};
+    F.rs_flags = c->d_rs_flags.p + D.res_base;
+    F.rs_tgt = c->d_rs_tgt.p + D.res_base;
+    F.rs_state = c->d_rs_state.p + D.res_base;
+    F.rs_slot = c->d_rs_slot.p + D.res_base;
+    F.pt_data = c->d_pt_data.p + (size_t)D.point_base * LDSO_BA_POINT_STRIDE;
+    F.pt_out = c->d_pt_out.p + (size_t)D.point_base * 12;
+    F.pt_host = c->d_pt_host.p + D.point_base;
+    F.num_good = dp + o_ng;
+    F.last_res = dp + o_lr;
+    F.last_state = reinterpret_cast<const int8_t *>(dp + o_ls);
+    F.frame_flagged = reinterpret_cast<const uint8_t *>(dp + o_ff);
+    F.cnt = dp + o_cnt;
+    F.counts = dp + o_counts;
+    F.num_good_out = dp + o_ngo;
+    F.status = reinterpret_cast<int8_t *>(dp + o_st);
+    F.ls_out = reinterpret_cast<int8_t *>(dp + o_lso);
+    F.res_live = reinterpret_cast<uint8_t *>(dp + o_live);
+    F.R = R;
+    F.P = P;
+    F.rec_base = D.rec_base;
+    F.min_good_active = fp.min_good_active_res_for_marg;
+    F.min_good = fp.min_good_res_for_marg;
+    F.min_idepth_h = fp.min_idepth_h_marg;
+    if (R) k_flag_count<<<(R + 255) / 256, 256, 0, c->stream>>>(F);
+    if (P) k_flag_decide<<<(P + 255) / 256, 256, 0, c->stream>>>(F);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hp + o_counts, dp + o_counts, (n_words - o_counts) * w4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (counts) std::memcpy(counts, hp + o_counts, 4 * w4);
+    const int8_t *h_st = reinterpret_cast<const int8_t *>(hp + o_st), *h_lso = reinterpret_cast<const int8_t *>(hp + o_lso);
+    for (int q = 0; q < P; q++) {
+        const int p = H.pt_orig[q];
+        if (status) status[p] = h_st[q];
+        if (num_good_out) num_good_out[p] = hp[o_ngo + q];
+        if (last_state_out) {
+            last_state_out[2 * p] = h_lso[2 * q];
+            last_state_out[2 * p + 1] = h_lso[2 * q + 1];
+        }
+    }
+    if (res_live) {
+        const uint8_t *h_live = reinterpret_cast<const uint8_t *>(hp + o_live);
+        for (int pos = 0; pos < R; pos++) res_live[H.rs_orig[pos]] = h_live[pos];
+    }
+    return 0;
 }
 
 // ---- frame store ----------------------------------------------------------------------------
