@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "../../include/ldso_ct.h"
+#include "ct_eval.h"
 #include "se3.h"
 
 namespace ldso_ct {
@@ -180,11 +181,10 @@ LDSO_HD inline void lm_step(const double *H, const double *b, float lambda, cons
     lm_increment(H, b, lambda, p, W, inc);
     float extrapFac = 1;
     if (lambda < kLambdaExtrapolationLimit) extrapFac = sqrtf(sqrtf(kLambdaExtrapolationLimit / lambda));
-    const float scale[8] = {0.5f, 0.5f, 0.5f, 1.0f, 1.0f, 1.0f, 10.0f, 1000.0f};  // SCALE_XI_TRANS, _ROT, _A, _B
     double incScaled[8], sq = 0;
     for (int i = 0; i < 8; i++) {
         inc[i] = inc[i] * extrapFac;
-        incScaled[i] = inc[i] * scale[i];
+        incScaled[i] = inc[i] * kCtScale[i];  // SCALE_XI_TRANS, _ROT, _A, _B
         sq = sq + incScaled[i] * incScaled[i];
     }
     if (!isfinite(sq))

@@ -1,14 +1,14 @@
 // k_ct_track.h -- trackNewestCoarse's whole LM loop (CoarseTracker.cc:61-310) in one launch:
 //   k_ct_track   grid.x = starts, one workgroup per start.  The workgroup walks the levels and the LM
 //                iterations itself: all lanes evaluate calcRes + calcGSSSE at the pose lane 0 set up
-//                (k_ct_calc_res<true>'s per-point statements, contraction off, nothing written per
+//                (ct_res_point, the function k_ct_calc_res<true> calls, with nothing written per
 //                point), lane 0 runs ct_lm.h's state machine on the sums.  No workgroup reads what
 //                another wrote: the only synchronisation is __syncthreads() and the kernel boundary.
 // The sums are bitwise those of ldso_ct_calc_res_gs: a chunk of 256 consecutive points is that
 // kernel's block -- each wave reduced in double with the xor tree, the four waves combined as
 // (w0 + w1) + (w2 + w3) -- and the chunk partials are added in chunk order in double; a workgroup
-// of kWaves wavefronts takes kWaves / 4 chunks per sweep.  finish_calc_res / finish_calc_gs's
-// statements then run on the device (ct_track_finish).
+// of kWaves wavefronts takes kWaves / 4 chunks per sweep.  The constants of an evaluation and the
+// Vec6, H and b from its sums are ct_eval.h's, the same functions the host entry points call.
 #pragma once
 #include <cstdint>
 
@@ -19,20 +19,14 @@
 
 namespace {
 
-constexpr int kTrackWaves = 8;  // 512 lanes, two chunks per sweep: 149 VGPRs per lane, no spill
+constexpr int kTrackWaves = 8;  // 512 lanes, two chunks per sweep: 147 VGPRs per lane, no spill
 constexpr int kTrackSums = kResParts + kGsParts;
 
-struct CtTrackLevel {
-    const float4 *__restrict__ pc;
-    const float4 *__restrict__ img;
-    int n, wl, hl;
-    float fxl, fyl, cxl, cyl, Ki[9];
-};
 struct CtTrackStart {  // one start, in mapped host memory
     double ref_to_new[12], aff[2], min_res[5];
 };
 struct CtTrackParams {
-    CtTrackLevel lv[5];
+    CtLevel lv[5];
     ldso_ct_track_params p;
     const CtTrackStart *starts;
     ldso_ct_track_result *out;
@@ -43,116 +37,28 @@ struct CtTrackParams {
 };
 struct CtTrackEval {  // what lane 0 hands to the sweep
     CtPose pose;
-    float gs_a, gs_b0, cutoffTH, maxEnergy;
+    CtEvalTerms ev;
     int lvl, more;
 };
 
-// make_pose and gs_affine (ldso_ct.hip) for the evaluation the state machine asks for
+// the constants of the evaluation the state machine asks for
 __device__ inline void ct_track_setup(const CtTrackParams &P, const ldso_ct::Track &T, CtTrackEval &E) {
-    const CtTrackLevel &L = P.lv[T.lvl];
-    float R[9], t[3];
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) R[3 * i + j] = (float)T.eval_pose[4 * i + j];
-        t[i] = (float)T.eval_pose[4 * i + 3];
-    }
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++)
-            E.pose.RKi[3 * i + j] = R[3 * i] * L.Ki[j] + R[3 * i + 1] * L.Ki[3 + j] + R[3 * i + 2] * L.Ki[6 + j];
-    for (int i = 0; i < 3; i++) E.pose.t[i] = t[i];
-    ldso_ba::affine_from_to(P.ref_exposure, P.new_exposure, P.ref_a, P.ref_b, T.eval_aff[0], T.eval_aff[1], E.pose.aLL,
-                            E.pose.bLL);
-    E.gs_a = (float)(double)E.pose.aLL;
-    E.gs_b0 = P.ref_b;
-    E.cutoffTH = T.cutoff();
-    E.maxEnergy = 2 * kHuberTH * E.cutoffTH - kHuberTH * kHuberTH;
+    ldso_ct::ct_eval_setup(T.eval_pose, P.lv[T.lvl].Ki, P.ref_exposure, P.new_exposure, P.ref_a, P.ref_b, T.eval_aff[0],
+                           T.eval_aff[1], T.cutoff(), E.pose, E.ev);
     E.lvl = T.lvl;
 }
 
-// k_ct_calc_res<true>'s statements for point i: the kResParts terms into acc, Accumulator9's into gs
-__device__ __forceinline__ void ct_track_point(const CtTrackLevel &P, const CtTrackEval &E, int i, double *acc,
-                                               double *gs) {
-    const CtPose &T = E.pose;
-    const float4 q = P.pc[i];
-    const float x = q.x, y = q.y, id = q.z;
-    const float *RKi = T.RKi, *t = T.t;
-    float pt[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) pt[k] = (RKi[3 * k] * x + RKi[3 * k + 1] * y + RKi[3 * k + 2] * 1) + t[k] * id;
-    const float u = pt[0] / pt[2], v = pt[1] / pt[2];
-    const float Ku = P.fxl * u + P.cxl, Kv = P.fyl * v + P.cyl;
-    const float new_idepth = id / pt[2];
-    if (E.lvl == 0 && i % 32 == 0) {  // CoarseTracker.cc:583-619
-        float ptT[3], ptT2[3], pt3[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float kx = P.Ki[3 * k] * x + P.Ki[3 * k + 1] * y + P.Ki[3 * k + 2] * 1;
-            ptT[k] = kx + t[k] * id;
-            ptT2[k] = kx - t[k] * id;
-            pt3[k] = (RKi[3 * k] * x + RKi[3 * k + 1] * y + RKi[3 * k + 2] * 1) - t[k] * id;
-        }
-        const float uT = ptT[0] / ptT[2], vT = ptT[1] / ptT[2];
-        const float KuT = P.fxl * uT + P.cxl, KvT = P.fyl * vT + P.cyl;
-        const float uT2 = ptT2[0] / ptT2[2], vT2 = ptT2[1] / ptT2[2];
-        const float KuT2 = P.fxl * uT2 + P.cxl, KvT2 = P.fyl * vT2 + P.cyl;
-        const float u3 = pt3[0] / pt3[2], v3 = pt3[1] / pt3[2];
-        const float Ku3 = P.fxl * u3 + P.cxl, Kv3 = P.fyl * v3 + P.cyl;
-        const float sT = (KuT - x) * (KuT - x) + (KvT - y) * (KvT - y);
-        const float sT2 = (KuT2 - x) * (KuT2 - x) + (KvT2 - y) * (KvT2 - y);
-        const float sRT = (Ku - x) * (Ku - x) + (Kv - y) * (Kv - y);
-        const float sRT2 = (Ku3 - x) * (Ku3 - x) + (Kv3 - y) * (Kv3 - y);
-        acc[3] = (double)sT + (double)sT2;
-        acc[4] = (double)sRT + (double)sRT2;
-        acc[5] = 2;
-    }
-    if (Ku > 2 && Kv > 2 && Ku < P.wl - 3 && Kv < P.hl - 3 && new_idepth > 0) {
-        const float refColor = q.w;
-        // getInterpolatedElement33 (GlobalFuncs.h:89-103)
-        const int ix = (int)Ku, iy = (int)Kv;
-        const float dx = Ku - ix, dy = Kv - iy, dxdy = dx * dy;
-        const float4 *bp = P.img + ix + (size_t)iy * P.wl;
-        const float4 t11 = bp[1 + P.wl], t01 = bp[P.wl], t10 = bp[1], t00 = bp[0];
-        const float w11 = dxdy, w01 = dy - dxdy, w10 = dx - dxdy, w00 = 1 - dx - dy + dxdy;
-        const float h0 = w11 * t11.x + w01 * t01.x + w10 * t10.x + w00 * t00.x;
-        const float h1 = w11 * t11.y + w01 * t01.y + w10 * t10.y + w00 * t00.y;
-        const float h2 = w11 * t11.z + w01 * t01.z + w10 * t10.z + w00 * t00.z;
-        if (isfinite(h0)) {
-            const float residual = h0 - (float)(T.aLL * refColor + T.bLL);
-            const float hw = fabsf(residual) < kHuberTH ? 1 : kHuberTH / fabsf(residual);
-            acc[1] = 1;
-            if (fabsf(residual) > E.cutoffTH) {
-                acc[0] = E.maxEnergy;
-                acc[2] = 1;
-            } else {
-                acc[0] = hw * residual * residual * (2 - hw);
-                acc[6] = 1;
-                ct_gs_terms(new_idepth, u, v, h1 * P.fxl, h2 * P.fyl, E.gs_a, E.gs_b0, refColor, residual, hw, gs);
-            }
-        }
-    }
-}
-
-// finish_calc_res and finish_calc_gs (ldso_ct.hip) from the sums s [kTrackSums], one output per lane
+// the Vec6, H and b from the sums s [kTrackSums], one output per lane
 __device__ inline void ct_track_finish(const double *s, int tid, double *rs, double *H, double *b) {
-    const float scale[8] = {0.5f, 0.5f, 0.5f, 1.0f, 1.0f, 1.0f, 10.0f, 1000.0f};  // SCALE_XI_TRANS, _ROT, _A, _B
     if (tid < 72) {
         const int r = tid < 64 ? tid / 8 : tid - 64, cc = tid < 64 ? tid % 8 : 8;
-        const int lo = r < cc ? r : cc, hi = r < cc ? cc : r;
-        const float Hrc = (float)s[kResParts + lo * 9 - lo * (lo - 1) / 2 + (hi - lo)];
-        const int nw = ((int)s[6] + 3) / 4 * 4;  // buf_warped_n
-        const double inv_n = (double)(1.0f / nw);
+        const double e = ldso_ct::ct_finish_gs_entry(s + kResParts, (int)s[6], r, cc);
         if (tid < 64)
-            H[tid] = (double)Hrc * inv_n * scale[cc] * scale[r];
+            H[tid] = e;
         else
-            b[r] = (double)Hrc * inv_n * scale[r];
+            b[r] = e;
     } else if (tid == 72) {
-        const float E = (float)s[0], sT = (float)s[3], sRT = (float)s[4], sNum = (float)s[5];
-        const int nE = (int)s[1], nSat = (int)s[2];
-        rs[0] = E;
-        rs[1] = nE;
-        rs[2] = sT / (sNum + 0.1);
-        rs[3] = 0;
-        rs[4] = sRT / (sNum + 0.1);
-        rs[5] = nSat / (float)nE;
+        ldso_ct::ct_finish_res(s, rs);
     }
 }
 
@@ -227,7 +133,7 @@ __global__ __launch_bounds__(kWaves *kWave) void k_ct_track(CtTrackParams P) {
     }
     __syncthreads();
     for (;;) {
-        const CtTrackLevel &L = P.lv[E.lvl];
+        const CtLevel &L = P.lv[E.lvl];
         const int nb = L.n > 0 ? (L.n + kCtThreads - 1) / kCtThreads : 1;
         double tot = 0;
         for (int base = 0; base < nb; base += kChunks) {
@@ -235,7 +141,8 @@ __global__ __launch_bounds__(kWaves *kWave) void k_ct_track(CtTrackParams P) {
             double v[64];  // acc [kResParts] | gs [kGsParts] | zeros
 #pragma unroll
             for (int k = 0; k < 64; k++) v[k] = 0;
-            if (i < L.n) ct_track_point(L, E, i, v, v + kResParts);
+            float4 w0, w1;  // not formed: kWarp is false
+            if (i < L.n) ct_res_point<true, false>(L, E.pose, E.ev, E.lvl, i, v, v + kResParts, w0, w1);
             const double total = ct_track_wave_sums(v, lane);
             if (lane < kTrackSums) red[wv][lane] = total;
             __syncthreads();

@@ -1,7 +1,8 @@
 // ldso_ct.hip -- the C ABI of LDSO's coarse tracker (include/ldso_ct.h) on the MI355X (gfx950) and its
 // host side.  The kernels, each described where it stands:
 //   k_ct_pyramid.h       k_ct_pyr_down, k_ct_pyr_grad: the new frame's pyramid
-//   k_ct_residual.h      k_ct_calc_res, k_ct_calc_gs: calcRes / calcGSSSE
+//   k_ct_residual.h      k_ct_calc_res, k_ct_calc_gs: calcRes / calcGSSSE (ct_eval.h: an evaluation's constants and
+//                        the Vec6 / H / b from its sums, the same functions here and in k_ct_track)
 //   k_ct_immature.h      k_ct_make_immature, k_ct_trace, k_ct_ip_count: immature points
 //   k_ct_coarse_depth.h  k_ct_cd_*: the reference cloud from the window's contributions
 //   k_ct_select.h        k_ct_sel_*: pixel selection (makeMaps) and makeNewTraces' walk
@@ -35,21 +36,9 @@
 
 #pragma clang fp contract(off)
 
-namespace {
-
-constexpr float kScaleXiRot = 1.0f, kScaleXiTrans = 0.5f, kScaleA = 10.0f, kScaleB = 1000.0f;  // Settings.h:29-35
-
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-void affine_from_to(float expF, float expT, float aF, float bF, float aT, float bT, float &a, float &b) {
-    if (expF == 0 || expT == 0) expT = expF = 1;  // AffLight::fromToVecExposure (AffLight.h:27-35)
-    a = std::exp(aT - aF) * expT / expF;
-    b = bT - a * bF;
-}
-
-}  // namespace
-
 // the BA frame store's view of the new frame (ldso_ba_frame_put_tracker)
 int ldso_ba::ct_frame_view(const ldso_ct_ctx *c, ldso_ba::CtFrameView *out) {
     if (!c || !out) return fail(-1, "null argument");
@@ -100,29 +89,36 @@ LevelGrid level_grid(const ldso_ct_ctx *c, int lvl) {
     return {n, std::max(1, (n + kCtThreads - 1) / kCtThreads)};
 }
 
-// calcGSSSE's affine pair (CoarseTracker.cc:683-687): a = the float of fromToVecExposure's aLL, b0 = the
-// reference's b
-void gs_affine(const ldso_ct_ctx *c, double aff_a, double aff_b, float &a, float &b0) {
-    float aLL, bLL;
-    affine_from_to(c->ref_exposure, c->new_exposure, c->ref_a, c->ref_b, (float)aff_a, (float)aff_b, aLL, bLL);
-    a = (float)(double)aLL;
-    b0 = c->ref_b;
+// a level as the kernels read it
+CtLevel level_of(const ldso_ct_ctx *c, int lvl) {
+    CtLevel L;
+    L.pc = c->d_pc.p + c->pc_off[lvl];
+    L.img = c->d_dIp.p + c->pyr.off[lvl];
+    L.n = level_grid(c, lvl).n;
+    L.wl = c->pyr.wl[lvl];
+    L.hl = c->pyr.hl[lvl];
+    L.fxl = c->fx[lvl];
+    L.fyl = c->fy[lvl];
+    L.cxl = c->cx[lvl];
+    L.cyl = c->cy[lvl];
+    for (int k = 0; k < 9; k++) L.Ki[k] = c->Ki[lvl][k];
+    return L;
 }
 
-// the per-hypothesis constants of calcRes (CoarseTracker.cc:555-558), float as the reference
-void make_pose(const ldso_ct_ctx *c, int lvl, const double *T, float aff_a, float aff_b, CtPose &p) {
-    float R[9], t[3];
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) R[3 * i + j] = (float)T[4 * i + j];
-        t[i] = (float)T[4 * i + 3];
-    }
-    const float *Ki = c->Ki[lvl];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++)
-            p.RKi[3 * i + j] = R[3 * i] * Ki[j] + R[3 * i + 1] * Ki[3 + j] + R[3 * i + 2] * Ki[6 + j];
-    for (int i = 0; i < 3; i++) p.t[i] = t[i];
-    affine_from_to(c->ref_exposure, c->new_exposure, c->ref_a, c->ref_b, aff_a, aff_b, p.aLL, p.bLL);
-    p.pad[0] = p.pad[1] = 0;
+// ct_eval_setup for the context's reference and new frame: the pose of one hypothesis, and the terms every
+// hypothesis under this cutoff shares
+CtEvalTerms make_pose(const ldso_ct_ctx *c, int lvl, const double *T, double aff_a, double aff_b, float cutoffTH, CtPose &p) {
+    CtEvalTerms e;
+    ldso_ct::ct_eval_setup(T, c->Ki[lvl], c->ref_exposure, c->new_exposure, c->ref_a, c->ref_b, (float)aff_a, (float)aff_b,
+                           cutoffTH, p, e);
+    return e;
+}
+
+// calcGSSSE's affine pair alone: it reads neither the pose nor the cutoff
+CtEvalTerms gs_affine(const ldso_ct_ctx *c, int lvl, double aff_a, double aff_b) {
+    const double T0[12] = {0};
+    CtPose unused;
+    return make_pose(c, lvl, T0, aff_a, aff_b, 0, unused);
 }
 
 int check_level(const ldso_ct_ctx *c, int lvl) {
@@ -134,46 +130,32 @@ int check_level(const ldso_ct_ctx *c, int lvl) {
     return 0;
 }
 
-// launch calcRes for n_hyp poses already staged in h_poses (partials to parts[0, n_hyp*nb*8))
+// launch calcRes for n_hyp poses already staged in h_poses by make_pose, which returned ev (partials to
+// parts[0, n_hyp*nb*8))
 // gs (n_hyp == 1): the pose by value and calcGSSSE in the same kernel (k_ct_calc_res<true>), its
 // partials at parts + n_hyp * nb * kResParts
-int launch_calc_res(ldso_ct_ctx *c, int lvl, int n_hyp, float cutoffTH, bool write_warp, size_t extra_parts,
-                    bool gs = false, double aff_a = 0, double aff_b = 0) {
-    const auto [n, nb] = level_grid(c, lvl);
+int launch_calc_res(ldso_ct_ctx *c, int lvl, int n_hyp, const CtEvalTerms &ev, bool write_warp, size_t extra_parts,
+                    bool gs = false) {
+    const int nb = level_grid(c, lvl).nb;
     int rc = ct_grow(c, c->parts, (size_t)n_hyp * nb * kResParts + extra_parts);
     if (rc) return rc;
     if (!gs)
         HIP_TRY(hipMemcpyAsync(c->d_poses.p, c->h_poses.p, (size_t)n_hyp * sizeof(CtPose), hipMemcpyHostToDevice,
                                c->stream));
     CtResParams P;
-    P.pc = c->d_pc.p + c->pc_off[lvl];
-    P.img = c->d_dIp.p + c->pyr.off[lvl];
+    P.lv = level_of(c, lvl);
     P.poses = c->d_poses.p;
     P.state = c->d_state.p;
     P.warp = c->d_warp.p;
     P.parts = c->parts.dev;
-    P.n = n;
-    P.wl = c->pyr.wl[lvl];
-    P.hl = c->pyr.hl[lvl];
     P.lvl = lvl;
     P.write_warp = write_warp ? 1 : 0;
     P.n_blocks = nb;
-    P.fxl = c->fx[lvl];
-    P.fyl = c->fy[lvl];
-    P.cxl = c->cx[lvl];
-    P.cyl = c->cy[lvl];
-    P.cutoffTH = cutoffTH;
-    P.maxEnergy = 2 * kHuberTH * cutoffTH - kHuberTH * kHuberTH;  // CoarseTracker.cc:565-566
-    for (int k = 0; k < 9; k++) P.Ki[k] = c->Ki[lvl][k];
+    P.ev = ev;
     P.pose0 = c->h_poses.p[0];
     P.gs_parts = c->parts.dev + (size_t)n_hyp * nb * kResParts;
-    P.gs_a = 0;
-    P.gs_b0 = 0;
     const dim3 grid(nb, gs ? 1 : n_hyp);
-    if (gs) {
-        gs_affine(c, aff_a, aff_b, P.gs_a, P.gs_b0);
-        return ct_launch(c, kCtSlotCalcRes, [&] { k_ct_calc_res<true><<<grid, kCtThreads, 0, c->stream>>>(P); });
-    }
+    if (gs) return ct_launch(c, kCtSlotCalcRes, [&] { k_ct_calc_res<true><<<grid, kCtThreads, 0, c->stream>>>(P); });
     return ct_launch(c, kCtSlotCalcRes, [&] { k_ct_calc_res<false><<<grid, kCtThreads, 0, c->stream>>>(P); });
 }
 
@@ -185,22 +167,13 @@ void finish_calc_res(ldso_ct_ctx *c, int lvl, int n_hyp, bool write_warp, double
         const double *p = c->parts.p + (size_t)hI * nb * kResParts;
         for (int b = 0; b < nb; b++)
             for (int k = 0; k < kResParts; k++) s[k] += p[(size_t)b * kResParts + k];
-        // Vec6 of CoarseTracker.cc:662-670; E and the shift sums are floats in the reference
-        const float E = (float)s[0], sT = (float)s[3], sRT = (float)s[4], sNum = (float)s[5];
-        const int nE = (int)s[1], nSat = (int)s[2];
-        double *rs = rs_out + 6 * (size_t)hI;
-        rs[0] = E;
-        rs[1] = nE;
-        rs[2] = sT / (sNum + 0.1);
-        rs[3] = 0;
-        rs[4] = sRT / (sNum + 0.1);
-        rs[5] = nSat / (float)nE;
+        ldso_ct::ct_finish_res(s, rs_out + 6 * (size_t)hI);
         if (write_warp && hI == 0) c->last_warped = (int)s[6];
     }
 }
 
-int run_calc_res(ldso_ct_ctx *c, int lvl, int n_hyp, float cutoffTH, bool write_warp, double *rs_out) {
-    int rc = launch_calc_res(c, lvl, n_hyp, cutoffTH, write_warp, 0);
+int run_calc_res(ldso_ct_ctx *c, int lvl, int n_hyp, const CtEvalTerms &ev, bool write_warp, double *rs_out) {
+    int rc = launch_calc_res(c, lvl, n_hyp, ev, write_warp, 0);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));  // the partials are in parts.p already
     finish_calc_res(c, lvl, n_hyp, write_warp, rs_out);
@@ -210,6 +183,7 @@ int run_calc_res(ldso_ct_ctx *c, int lvl, int n_hyp, float cutoffTH, bool write_
 // calcGSSSE launch over the warped buffers, partials at parts + off
 int launch_calc_gs(ldso_ct_ctx *c, int lvl, double aff_a, double aff_b, size_t off) {
     const LevelGrid g = level_grid(c, lvl);
+    const CtEvalTerms e = gs_affine(c, lvl, aff_a, aff_b);
     CtGsParams P;
     P.state = c->d_state.p;
     P.warp = c->d_warp.p;
@@ -217,27 +191,20 @@ int launch_calc_gs(ldso_ct_ctx *c, int lvl, double aff_a, double aff_b, size_t o
     P.n = g.n;
     P.fxl = c->fx[lvl];
     P.fyl = c->fy[lvl];
-    gs_affine(c, aff_a, aff_b, P.a, P.b0);
+    P.a = e.gs_a;
+    P.b0 = e.gs_b0;
     return ct_launch(c, kCtSlotCalcGs, [&] { k_ct_calc_gs<<<g.nb, kCtThreads, 0, c->stream>>>(P); });
 }
 
-// Accumulator9::finish + CoarseTracker.cc:725-740 from the GS block partials on the host
+// the scaled H, b from the GS block partials on the host and the last calcRes' warped count
 void finish_calc_gs(ldso_ct_ctx *c, int lvl, const double *parts, double *H_out, double *b_out) {
     const int nb = level_grid(c, lvl).nb;
     double s[kGsParts] = {0};
     for (int b = 0; b < nb; b++)
         for (int k = 0; k < kGsParts; k++) s[k] += parts[(size_t)b * kGsParts + k];
-    float H[9][9];
-    int k = 0;
-    for (int r = 0; r < 9; r++)
-        for (int cc = r; cc < 9; cc++, k++) H[r][cc] = H[cc][r] = (float)s[k];
-    const int nw = (c->last_warped + 3) / 4 * 4;  // buf_warped_n (padded to a multiple of 4)
-    const double inv_n = (double)(1.0f / nw);
-    const float scale[8] = {kScaleXiTrans, kScaleXiTrans, kScaleXiTrans, kScaleXiRot,
-                            kScaleXiRot,   kScaleXiRot,   kScaleA,       kScaleB};
     for (int r = 0; r < 8; r++) {
-        for (int cc = 0; cc < 8; cc++) H_out[8 * r + cc] = (double)H[r][cc] * inv_n * scale[cc] * scale[r];
-        b_out[r] = (double)H[r][8] * inv_n * scale[r];
+        for (int cc = 0; cc < 8; cc++) H_out[8 * r + cc] = ldso_ct::ct_finish_gs_entry(s, c->last_warped, r, cc);
+        b_out[r] = ldso_ct::ct_finish_gs_entry(s, c->last_warped, r, 8);
     }
 }
 
@@ -1138,8 +1105,7 @@ int ldso_ct_calc_res(ldso_ct_ctx *c, int32_t lvl, const double ref_to_new[12], d
     if (rc) return rc;
     if (!ref_to_new || !rs_out) return fail(-1, "null argument");
     HIP_TRY(hipSetDevice(c->device));
-    make_pose(c, lvl, ref_to_new, (float)aff_a, (float)aff_b, c->h_poses.p[0]);
-    rc = run_calc_res(c, lvl, 1, cutoff_th, true, rs_out);
+    rc = run_calc_res(c, lvl, 1, make_pose(c, lvl, ref_to_new, aff_a, aff_b, cutoff_th, c->h_poses.p[0]), true, rs_out);
     if (rc) return rc;
     c->last_lvl = lvl;
     return 0;
@@ -1152,9 +1118,10 @@ int ldso_ct_calc_res_batch(ldso_ct_ctx *c, int32_t lvl, int32_t n_hyp, const dou
     if (!ref_to_new || !aff_ab || !rs_out) return fail(-1, "null argument");
     if (n_hyp < 1 || n_hyp > kMaxHyp) return fail(-1, "n_hyp out of range [1, 256]");
     HIP_TRY(hipSetDevice(c->device));
+    CtEvalTerms ev;
     for (int k = 0; k < n_hyp; k++)
-        make_pose(c, lvl, ref_to_new + 12 * k, (float)aff_ab[2 * k], (float)aff_ab[2 * k + 1], c->h_poses.p[k]);
-    return run_calc_res(c, lvl, n_hyp, cutoff_th, false, rs_out);
+        ev = make_pose(c, lvl, ref_to_new + 12 * k, aff_ab[2 * k], aff_ab[2 * k + 1], cutoff_th, c->h_poses.p[k]);
+    return run_calc_res(c, lvl, n_hyp, ev, false, rs_out);
 }
 
 int ldso_ct_calc_gs(ldso_ct_ctx *c, int32_t lvl, const double ref_to_new[12], double aff_a, double aff_b,
@@ -1182,10 +1149,10 @@ int ldso_ct_calc_res_gs(ldso_ct_ctx *c, int32_t lvl, const double ref_to_new[12]
     HIP_TRY(hipSetDevice(c->device));
     const int nb = level_grid(c, lvl).nb;
     const size_t res_parts = (size_t)nb * kResParts;
-    make_pose(c, lvl, ref_to_new, (float)aff_a, (float)aff_b, c->h_poses.p[0]);
+    const CtEvalTerms ev = make_pose(c, lvl, ref_to_new, aff_a, aff_b, cutoff_th, c->h_poses.p[0]);
     // calcRes and calcGSSSE in one launch (the GS terms of each warped point from the same values
     // the warped buffers receive; the block partials are those of k_ct_calc_gs)
-    rc = launch_calc_res(c, lvl, 1, cutoff_th, true, (size_t)nb * kGsParts, true, aff_a, aff_b);
+    rc = launch_calc_res(c, lvl, 1, ev, true, (size_t)nb * kGsParts, true);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));  // the partials are in parts.p already
     finish_calc_res(c, lvl, 1, true, rs_out);
@@ -1222,19 +1189,7 @@ int ldso_ct_track(ldso_ct_ctx *c, int32_t n, const double *ref_to_new_in, const 
         std::memcpy(S.min_res, min_res_for_abort + 5 * (size_t)k, sizeof S.min_res);
     }
     CtTrackParams P{};
-    for (int l = 0; l <= coarsest_lvl; l++) {
-        CtTrackLevel &L = P.lv[l];
-        L.pc = c->d_pc.p + c->pc_off[l];
-        L.img = c->d_dIp.p + c->pyr.off[l];
-        L.n = level_grid(c, l).n;
-        L.wl = c->pyr.wl[l];
-        L.hl = c->pyr.hl[l];
-        L.fxl = c->fx[l];
-        L.fyl = c->fy[l];
-        L.cxl = c->cx[l];
-        L.cyl = c->cy[l];
-        for (int k = 0; k < 9; k++) L.Ki[k] = c->Ki[l][k];
-    }
+    for (int l = 0; l <= coarsest_lvl; l++) P.lv[l] = level_of(c, l);
     P.p = p;
     P.starts = c->track_in.dev;
     P.out = c->track_out.dev;

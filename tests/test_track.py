@@ -161,6 +161,30 @@ def test_batch_equals_single_calls(built):
     ct.close()
 
 
+def test_calc_res_paths_agree_on_one_pose(built):
+    """k_ct_calc_res<false> (ldso_ct_calc_res), <true> (ldso_ct_calc_res_gs) and k_ct_track's sweep are
+    instantiations of one per-point function; the lock-step pins the last two to each other, this pins the first
+    two, and k_ct_calc_gs over the records the first leaves: the same Vec6, the same warped records, the same
+    H and b, bit for bit.  300 points at level 0: two blocks, the second ragged, the shift terms of every 32nd
+    point, and points that leave the image, saturate and warp."""
+    sc = S.scene("kitti", 7)
+    ct = sc.tracker()
+    T, ab = S.pose(9, 4.0), (S.REF_AB[0] + 0.05, S.REF_AB[1] + 2.0)
+    n = sc.pcs[0]["u"].size
+    rs = ct.calc_res(0, T, ab, 20.0)
+    warped = ct.warped()
+    H, b = ct.calc_gs(0, T, ab)
+    rs2, H2, b2 = ct.calc_res_gs(0, T, ab, 20.0)
+    warped2 = ct.warped()
+    n_sat = round(rs[5] * rs[1])
+    print(f"{n} points: {int(rs[1])} in the image, {n_sat} saturated, shift terms {rs[2]:.4g} / {rs[4]:.4g}")
+    assert n == 300 and 0 < n_sat < rs[1] < n and rs[2] > 0 and rs[4] > 0
+    assert len(warped) == (int(rs[1]) - n_sat + 3) // 4 * 4
+    assert _same_bits(rs, rs2) and _same_bits(warped, warped2)
+    assert _same_bits(H, H2) and _same_bits(b, b2) and np.all(np.isfinite(H)) and np.abs(b).max() > 0
+    ct.close()
+
+
 def test_refusals_repeatability_and_trace_capacity(built):
     from ldso_amd.tracker import CoarseTracker
 
