@@ -132,6 +132,13 @@ int ldso_ba_frame_precalc(int32_t n_frames, const ldso_ba_frame_state *frames, c
 int ldso_ba_set_adjoints(int32_t n_frames, const ldso_ba_frame_state *frames, double *ad_host,
                          double *ad_target, double *c_prior);
 
+/* 1 if every 8x8 block of an [N*N][64] adjoint array is diagonal -- its 56 off-diagonal entries
+ * equal zero exactly (-0.0 is zero, a denormal is not) --, 0 if not, < 0 on bad arguments.  This is
+ * the test ldso_ba_load, ldso_ba_update and ldso_ba_edit_window make of a window's ad_target:
+ * setAdjointsF's adTarget passes it, and the host stitch then scales by the diagonal instead of
+ * multiplying by the blocks; any other ad_target takes the dense products. */
+int ldso_ba_adjoints_diagonal(int32_t n_frames, const double *ad);
+
 /* FrameHessian::takeData (FrameHessian.cc:131-135): prior, delta, delta_prior [N][8].  The prior
  * (getPrior, FrameHessian.h:142-170) follows settings->affine_opt_mode_a / _b (NULL: the defaults);
  * settings are checked (ldso_ba_check_settings). */

@@ -170,6 +170,7 @@ ABI = [
     ("ldso_ba_last_error", C.c_char_p, []),
     ("ldso_ba_frame_precalc", C.c_int, [C.c_int32, C.c_void_p, f32p, f32p]),
     ("ldso_ba_set_adjoints", C.c_int, [C.c_int32, C.c_void_p, f64p, f64p, f64p]),
+    ("ldso_ba_adjoints_diagonal", C.c_int, [C.c_int32, f64p]),
     ("ldso_ba_frame_take_data", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, f64p, f64p, f64p]),
     ("ldso_ba_solve_system", C.c_int,
      [C.c_void_p, C.c_int32, C.c_int32, C.c_double, f64p, f64p, f64p, f64p, f64p, f64p, f64p, f64p, f64p, C.c_int32,

@@ -32,6 +32,7 @@ struct Switches {
     bool solve_lds;       // LDSO_BA_SOLVE_LDS: the LDS solve k_solve
     bool no_graph;        // LDSO_BA_NO_GRAPH: ldso_ba_optimize / _iterate launch directly
     bool iterate_graph;   // LDSO_BA_ITERATE_GRAPH: ldso_ba_iterate replays a captured graph
+    bool stitch_dense_adt;  // LDSO_BA_STITCH_DENSE_ADT: k_stitch_host multiplies by whole ad_target blocks, diagonal or not
 };
 Switches read_switches() {
     auto flag = [](const char *name) {
@@ -40,7 +41,7 @@ Switches read_switches() {
     };
     const char *hs = std::getenv("LDSO_BA_HS_SPLIT");
     return {flag("LDSO_BA_STITCH_RECORDS"), hs ? (hs[0] == '1' ? 1 : 0) : -1, flag("LDSO_BA_SOLVE_LDS"),
-            flag("LDSO_BA_NO_GRAPH"), flag("LDSO_BA_ITERATE_GRAPH")};
+            flag("LDSO_BA_NO_GRAPH"), flag("LDSO_BA_ITERATE_GRAPH"), flag("LDSO_BA_STITCH_DENSE_ADT")};
 }
 
 // ============================================================================================

@@ -318,10 +318,13 @@ size_t stitch_smem_bytes(int KP, int N, int *th_cap) {
 }
 
 // k_stitch_host dynamic LDS: the host block's staging for the largest window, at least the
-// frame-threshold staging of 1024 candidates (more if the host phase leaves room)
+// frame-threshold staging of 1024 candidates (more if the host phase leaves room).  Always the dense
+// path's size, the larger: which path a block takes is read on the device (WinDev::adt_diag), after
+// the launch -- and its LDS size -- may have been captured in a graph
 size_t stitch_host_smem_bytes(int N, int *th_cap) {
     const size_t th_fixed = th_fixed_bytes(kHsThreads);
-    size_t bytes = std::max(hs_lds_doubles(N) * sizeof(double), th_fixed + 1024 * sizeof(unsigned));
+    const size_t host = std::max(hs_lds_doubles(N, false), hs_lds_doubles(N, true)) * sizeof(double);
+    size_t bytes = std::max(host, th_fixed + 1024 * sizeof(unsigned));
     bytes = (bytes + 15) & ~(size_t)15;
     *th_cap = (int)((bytes - th_fixed) / sizeof(unsigned)) & ~3;
     return bytes;

@@ -160,7 +160,7 @@ bool same_desc(const WinDesc &a, const WinDesc &b) {
            a.KP == b.KP && a.ntiles == b.ntiles && a.p_all == b.p_all && a.sc_slab_base == b.sc_slab_base &&
            a.sys_base == b.sys_base && a.stage_base == b.stage_base && a.newest_begin == b.newest_begin &&
            a.newest_end == b.newest_end && a.rec_base == b.rec_base && a.vec_base == b.vec_base && a.width == b.width &&
-           a.height == b.height;
+           a.height == b.height && a.adt_diag == b.adt_diag;
 }
 }  // namespace
 

@@ -58,6 +58,7 @@ struct StitchParams {
     int th_cap;  // newest-frame energies staged in LDS by setNewFrameEnergyTH
     int pair_base;  // first global pair of this launch
     int hs_split;   // k_stitch_host: two blocks per host (Top / SC halves)
+    int dense_adt;  // k_stitch_host: the dense products for every window (else by WinDev::adt_diag)
     const int *__restrict__ frame_win;  // k_stitch_host: window of each global frame
     int frame_base;                     // k_stitch_host: first global host frame of this launch
     int win_base;   // first window of this launch

@@ -22,8 +22,21 @@ namespace {
 // where A_t is pair (i,t)'s 13x13 AccumulatorApprox block and D, E, EB, accHcc, accbc the blocks of
 // G_i = U^T diag(HdiF) U (k_point_sc's chunk partials summed in double).  Everything host i
 // reads is staged in LDS once: G_i (both triangles), the adjoints of the N pairs (i, k), the
-// N-1 Top accumulators; then X_jk = AT_ij D_jk (j <= k), S_j, TH_t = AH_it A_t, TT_t = AT_it A_t;
-// then every element of the partial.  Windows with more keyframes use k_stitch's records.
+// N-1 Top accumulators; then S_j and TH_t = AH_it A_t; then every element of the partial.  Windows
+// with more keyframes use k_stitch's records.
+//
+// The target adjoints.  setAdjointsF builds AT as a diagonal matrix, and the host marks a window
+// whose ad_target blocks are all diagonal (WinDev::adt_diag, set wherever ad_target is uploaded).
+// For such a window (the diagonal path) only the 8 diagonal entries at_k of every AT_ik are staged
+// and every product with an AT factor is the scaled element, left factor first:
+//   (AT_j M)[r][c] = at_j[r] M[r][c],   (M AT_k^T)[r][c] = M[r][c] at_k[c]
+// each product as fma(a, m, +0), which is what the dense sum of eight terms (seven of them exact
+// zeros) rounds to, the sign of a zero included.  The two paths differ only where M holds a
+// non-finite entry (the dense sum spreads it over the row, 0 * inf).  Any other window, and every
+// window under LDSO_BA_STITCH_DENSE_ADT (StitchParams::dense_adt), takes the dense path: the whole
+// AT blocks staged, X_jk = AT_ij D_jk (j <= k) and TT_t = AT_it A_t formed as 8x8 products.  The
+// choice is a block-uniform branch on data the block reads, so a captured graph follows an
+// ldso_ba_update of the adjoints; the launch always reserves the dense path's LDS.
 // ============================================================================================
 constexpr int kHostStitchMaxN = 11;
 constexpr int kHsThreads = 512;
@@ -37,9 +50,12 @@ __device__ __forceinline__ int hs_row(int r) { return 8 * r + ((r & 4) >> 1); }
 __host__ __device__ inline int hs_k5(int N) { return 8 * (N - 1) + 5; }
 __host__ __device__ inline int hs_ldg(int N) { return (hs_k5(N) + 1) & ~1; }  // even: 16-byte aligned rows
 __host__ __device__ inline int hs_npair(int N) { return (N - 1) * N / 2; }
-__host__ __device__ inline size_t hs_lds_doubles(int N) {
-    return (size_t)hs_k5(N) * hs_ldg(N) + 2 * kHsB * (size_t)N + 182 * (size_t)N + kHsB * (size_t)hs_npair(N) +
-           3 * kHsB * (size_t)N + 208 * (size_t)(N - 1);
+// the block's LDS in doubles (the regions: k_stitch_host); the diagonal path has no X and no TT and
+// keeps 8 entries of every AT.  75 KB dense and 56 KB diagonal at N = 7, 154 KB and 111 KB at N = 11.
+__host__ __device__ inline size_t hs_lds_doubles(int N, bool diag) {
+    const size_t n = (size_t)N;
+    return (size_t)hs_k5(N) * hs_ldg(N) + kHsB * n + (diag ? 8 : kHsB) * n + 182 * n +
+           (diag ? 0 : kHsB * (size_t)hs_npair(N)) + 2 * kHsB * n + (diag ? 0 : kHsB * n) + 208 * (n - 1);
 }
 // tile index t of the upper-tile order (a <= b) over nt tile rows -> (a, b)
 __device__ __forceinline__ void tile_ab(int t, int nt, int &a, int &b) {
@@ -117,16 +133,17 @@ __global__ __launch_bounds__(kHsThreads) void k_stitch_host(StitchParams P) {
     const int N = W.N, D = W.D, i = fr - W.frame_base, tid = threadIdx.x;
     const int Kc = 8 * (N - 1), K5 = Kc + 5, ldg = hs_ldg(N), nt = W.KP / 4, per = W.ntiles * 16;
     const int Nm1 = N - 1, npair = hs_npair(N);
+    const bool diag = W.adt_diag && !P.dense_adt;  // block-uniform: see the head of this file
     // LDS (every region an even number of doubles: 16-byte aligned rows for the b128 reads)
     double *Gd = sm;                     // [K5][ldg] G_i, both triangles
     double *AH = Gd + (size_t)K5 * ldg;  // [N][8][8] adH of pair (i, k)
-    double *AT = AH + kHsB * N;          // [N][8][8] adT of pair (i, k)
-    double *A14 = AT + kHsB * N;         // [N][13][14] pair (i, t)'s 13x13 Top block (t == i unused)
-    double *X = A14 + 182 * N;           // [npair][8][8] X_jk = AT_ij D_jk, target slots sj <= sk
-    double *SSt = X + kHsB * npair;      // [N][8][8] S_j^T, S_j = sum_k D_jk AH_ik^T
+    double *AT = AH + kHsB * N;          // [N][8][8] adT of pair (i, k); diagonal path: [N][8] its diagonal
+    double *A14 = AT + (diag ? 8 : kHsB) * N;  // [N][13][14] pair (i, t)'s 13x13 Top block (t == i unused)
+    double *X = A14 + 182 * N;           // [npair][8][8] X_jk = AT_ij D_jk, target slots sj <= sk (dense path)
+    double *SSt = X + (diag ? 0 : kHsB * npair);  // [N][8][8] S_j^T, S_j = sum_k D_jk AH_ik^T
     double *TH = SSt + kHsB * N;         // [N][8][8] AH_it A_t(88)
-    double *TT = TH + kHsB * N;          // [N][8][8] AT_it A_t(88)
-    double *HP = TT + kHsB * N;          // [2 parts][16 2x2s][N-1][4] the (i,i) block's per-term 2x2s
+    double *TT = TH + kHsB * N;          // [N][8][8] AT_it A_t(88) (dense path)
+    double *HP = TT + (diag ? 0 : kHsB * N);  // [2 parts][16 2x2s][N-1][4] the (i,i) block's per-term 2x2s
     double *CP = HP + 128 * (N - 1);     // [2 parts][40 items][N-1] the (calib, i) / b(i) per-term dots
     auto frame_of = [&](int slot) { return slot < i ? slot : slot + 1; };
     auto A_t = [&](int t, int r, int c) { return A14[182 * t + 14 * r + c]; };
@@ -177,7 +194,10 @@ __global__ __launch_bounds__(kHsThreads) void k_stitch_host(StitchParams P) {
             const size_t pk = (size_t)(W.pair_base + i + N * (e >> 6)) * 64 + (e & 63);
             const int eb = kHsB * (e >> 6) + hs_row((e >> 3) & 7) + (e & 7);
             AH[eb] = P.adH[pk];
-            AT[eb] = P.adT[pk];
+            if (!diag)
+                AT[eb] = P.adT[pk];
+            else if ((e & 63) % 9 == 0)
+                AT[8 * (e >> 6) + ((e >> 3) & 7)] = P.adT[pk];
         }
         // Top accumulators of the pairs (i, t): 24 float4 per item, summed over the pair's items
         for (int e = tid; e < (do_top ? 24 * Nm1 : 0); e += kHsThreads) {
@@ -217,10 +237,10 @@ __global__ __launch_bounds__(kHsThreads) void k_stitch_host(StitchParams P) {
     }
     __syncthreads();
     // ---- intermediates, 2x2 per thread, 16 threads per 8x8 block: S_j^T (N-1 blocks of N-1
-    // terms each, first), X_jk (sj <= sk), TH_t, TT_t ---------------------------------------
+    // terms each, first), TH_t and, on the dense path, X_jk (sj <= sk) and TT_t ---------------
     {
-        const int n_ss = do_sc ? Nm1 : 0, n_x = do_sc ? npair : 0, n_th = do_top ? Nm1 : 0;
-        const int total = 16 * (n_ss + n_x + 2 * n_th);
+        const int n_ss = do_sc ? Nm1 : 0, n_x = do_sc && !diag ? npair : 0, n_th = do_top ? Nm1 : 0;
+        const int total = 16 * (n_ss + n_x + (diag ? 1 : 2) * n_th);
         for (int u = tid; u < total; u += kHsThreads) {
             int blk = u >> 4;
             const int r0 = 2 * ((u & 15) >> 2), c0 = 2 * (u & 3);
@@ -319,7 +339,35 @@ __global__ __launch_bounds__(kHsThreads) void k_stitch_host(StitchParams P) {
             if (f1 == f2 && r0 > c0) continue;  // below the diagonal
             if (f1 == f2 && f1 == i) continue;  // the (i, i) block: per-term tasks above
             double v[2][2] = {{0, 0}, {0, 0}};
-            if (f1 == f2) {
+            if (diag) {  // the dense products below with diagonal AT: left scaling first, then right
+                const int s1 = f1 < i ? f1 : f1 - 1, s2 = f2 < i ? f2 : f2 - 1;
+                auto ld2 = [](const double *p) { return *reinterpret_cast<const double2 *>(p); };  // 16-byte aligned
+                const double2 l2 = ld2(AT + 8 * f1 + r0), r2 = ld2(AT + 8 * f2 + c0);
+                const double la[2] = {l2.x, l2.y}, ra[2] = {r2.x, r2.y};  // at_f1[r0 + a], at_f2[c0 + b]
+                if (f1 == i) {  // M at_f2, M = TH_f2 / S_f2^T: rows r0, r0 + 1 of its columns c0, c0 + 1
+                    const double *m = (top ? TH : SSt) + kHsB * f2 + hs_row(r0) + c0;
+                    const double2 m0 = ld2(m), m1 = ld2(m + 8);
+                    v[0][0] = fma(m0.x, ra[0], 0.0);
+                    v[0][1] = fma(m0.y, ra[1], 0.0);
+                    v[1][0] = fma(m1.x, ra[0], 0.0);
+                    v[1][1] = fma(m1.y, ra[1], 0.0);
+                } else if (f2 == i || !top || f1 == f2) {
+                    // the other factor transposed, m[b][a] = M[r0 + a][c0 + b]: TH_f1^T / S_f1 (f2 == i, no
+                    // right scaling), D_f1f2[r][c] = G[8 s2 + c][8 s1 + r], A_f1(4 + c, 4 + r)
+                    const double *m = f2 == i ? (top ? TH : SSt) + kHsB * f1 + hs_row(c0) + r0
+                                      : !top  ? Gd + (size_t)(8 * s2 + c0) * ldg + 8 * s1 + r0
+                                              : A14 + 182 * f1 + 14 * (4 + c0) + 4 + r0;
+                    const double2 m0 = ld2(m), m1 = ld2(m + (f2 == i ? 8 : !top ? ldg : 14));
+                    const double mm[2][2] = {{m0.x, m0.y}, {m1.x, m1.y}};
+#pragma unroll
+                    for (int a = 0; a < 2; a++)
+#pragma unroll
+                        for (int b = 0; b < 2; b++) {
+                            const double x = fma(la[a], mm[b][a], 0.0);
+                            v[a][b] = f2 == i ? x : fma(x, ra[b], 0.0);
+                        }
+                }
+            } else if (f1 == f2) {
                 const int f = f1, sf = f < i ? f : f - 1;
                 const double *tt = TT + kHsB * f + hs_row(r0), *at = AT + kHsB * f + hs_row(c0);
                 const double *x = top ? tt : xblk(sf, sf) + hs_row(r0);
@@ -354,8 +402,10 @@ __global__ __launch_bounds__(kHsThreads) void k_stitch_host(StitchParams P) {
         if (l0 < 32 * N) {  // (calib cc, frame f, rr)
             const int f = l0 >> 5, rr = (l0 >> 2) & 7, cc = l0 & 3;
             if (f == i) continue;  // per-term tasks above
-            {
-                const int sf = f < i ? f : f - 1;
+            const int sf = f < i ? f : f - 1;
+            if (diag) {
+                ha = fma(AT[8 * f + rr], top ? A_t(f, 4 + rr, cc) : Gd[(8 * sf + rr) * ldg + Kc + cc], 0.0);
+            } else {
 #pragma unroll
                 for (int k = 0; k < 8; k++)
                     ha += AT[kHsB * f + hs_row(rr) + k] * (top ? A_t(f, 4 + k, cc) : Gd[(8 * sf + k) * ldg + Kc + cc]);
@@ -364,8 +414,10 @@ __global__ __launch_bounds__(kHsThreads) void k_stitch_host(StitchParams P) {
         } else if (l0 < 40 * N) {  // b(f)[rr]
             const int f = (l0 - 32 * N) >> 3, rr = l0 & 7;
             if (f == i) continue;  // per-term tasks above
-            {
-                const int sf = f < i ? f : f - 1;
+            const int sf = f < i ? f : f - 1;
+            if (diag) {
+                ha = fma(AT[8 * f + rr], top ? A_t(f, 4 + rr, 12) : Gd[(8 * sf + rr) * ldg + Kc + 4], 0.0);
+            } else {
 #pragma unroll
                 for (int k = 0; k < 8; k++)
                     ha += AT[kHsB * f + hs_row(rr) + k] * (top ? A_t(f, 4 + k, 12) : Gd[(8 * sf + k) * ldg + Kc + 4]);

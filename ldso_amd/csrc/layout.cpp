@@ -87,6 +87,13 @@ void shard_points(const ldso_ba_window &in, int rank, int count, std::vector<int
     }
 }
 
+bool adjoints_diagonal(const double *ad, size_t n_blocks) {
+    for (size_t b = 0; b < n_blocks; b++)
+        for (int e = 0; e < 64; e++)
+            if (e % 9 != 0 && ad[b * 64 + e] != 0.0) return false;  // a NaN is not zero either
+    return true;
+}
+
 int build_layout(const ldso_ba_window *ws, int n_windows, int shard_rank, int shard_count, int item_order,
                  int top_chunk, bool marg, Layout &out, bool resident_frames) {
     for (int w = 0; w < n_windows; w++) {
@@ -257,6 +264,7 @@ int build_layout(const ldso_ba_window *ws, int n_windows, int shard_rank, int sh
         for (int i = 0; i < 4; i++) D.calib[i] = in.calib[i];
         for (int i = 0; i < 4; i++) D.cdelta[i] = in.c_delta[i];
         D.p_all = in.n_points;  // numID counts every shard's points
+        D.adt_diag = adjoints_diagonal(in.ad_target, (size_t)N * N) ? 1 : 0;
         D.K = 8 * (N - 1) + 5;
         D.KP = (D.K + 3) / 4 * 4;
         const int nt = D.KP / 4;

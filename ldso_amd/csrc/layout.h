@@ -29,6 +29,7 @@ struct WinDesc {
     float wM3, hM3;
     float calib[4];
     float cdelta[4];         // EnergyFunctional::cDeltaF (marginalisation pass only)
+    int adt_diag;            // every ad_target block of the window is diagonal (adjoints_diagonal): k_stitch_host scales
 };
 
 struct WinHost {
@@ -100,6 +101,10 @@ struct Layout {
     int chunk = 0, sc_chunk = 0;  // residuals per k_linearize wave, points per k_point_sc block
     size_t smem_max = 0;          // k_point_sc dynamic LDS of the widest window
 };
+
+// Whether each of the n_blocks 8x8 row-major blocks of `ad` has all 56 off-diagonal entries equal
+// to zero (exactly: -0.0 is zero, a denormal is not).  setAdjointsF's adTarget is (ldso_ba_set_adjoints).
+bool adjoints_diagonal(const double *ad, size_t n_blocks);
 
 // The ldso_ba_window contract (ldso_ba_validate_window); -1 and the thread's error message if not.
 int check_window(const ldso_ba_window &w, bool need_images = true);

@@ -142,6 +142,10 @@ int ldso_ba_set_adjoints(int32_t n, const ldso_ba_frame_state *f, double *adH, d
     if (n < 1 || n > LDSO_BA_MAX_FRAMES || !f || !adH || !adT) return fail(-1, "bad arguments");
     return set_adjoints(n, f, adH, adT, cp);
 }
+int ldso_ba_adjoints_diagonal(int32_t n, const double *ad) {
+    if (n < 1 || n > LDSO_BA_MAX_FRAMES || !ad) return fail(-1, "bad arguments");
+    return adjoints_diagonal(ad, (size_t)n * n) ? 1 : 0;
+}
 int ldso_ba_frame_take_data(int32_t n, const ldso_ba_frame_state *f, const ldso_ba_opt_settings *st, double *prior,
                             double *delta, double *dp) {
     if (n < 1 || n > LDSO_BA_MAX_FRAMES || !f) return fail(-1, "bad arguments");
@@ -646,6 +650,7 @@ int ldso_ba_update(ldso_ba_ctx *c, int32_t win, const ldso_ba_window *w) {
     const int N = H.N;
     HIP_TRY(hipSetDevice(c->device));
     for (int i = 0; i < 4; i++) D.calib[i] = w->calib[i];
+    D.adt_diag = adjoints_diagonal(w->ad_target, (size_t)N * N) ? 1 : 0;  // travels with the adjoints below
     H.c_prior.assign(w->c_prior, w->c_prior + 4);
     H.c_delta.assign(w->c_delta, w->c_delta + 4);
     H.frame_prior.assign(w->frame_prior, w->frame_prior + 8 * N);
@@ -863,6 +868,7 @@ static int linearize_pass(ldso_ba_ctx *c, int fix, int accumulate, int pass, con
     // two 512-thread blocks fit a CU: split the host blocks when the doubled grid still runs at once
     Sp.hs_split = Sp.n_win + 2 * c->n_frames <= 2 * c->n_cu ? 1 : 0;
     if (sw.hs_split >= 0) Sp.hs_split = sw.hs_split;  // tests: force either
+    Sp.dense_adt = sw.stitch_dense_adt ? 1 : 0;
     const bool hs = c->host_stitch;
     const int n_max = std::max(2, c->max_frames);
     const size_t st_smem = hs ? stitch_host_smem_bytes(n_max, &Sp.th_cap) : stitch_smem_bytes(c->kp_max, n_max, &Sp.th_cap);
@@ -1487,7 +1493,8 @@ std::vector<unsigned long long> capture_key(const ldso_ba_ctx *c, const Switches
     std::memcpy(&b, &c->settings.affine_opt_mode_b, 4);
     std::memcpy(&th, &c->settings.th_opt_iterations, 4);
     return {(unsigned long long)c->solve_exact, (unsigned long long)sw.solve_lds,
-            (unsigned long long)(sw.hs_split < 0 ? 0 : sw.hs_split == 1 ? 1 : 2), (unsigned long long)(unsigned)c->settings.solver_mode,
+            (unsigned long long)(sw.hs_split < 0 ? 0 : sw.hs_split == 1 ? 1 : 2), (unsigned long long)sw.stitch_dense_adt,
+            (unsigned long long)(unsigned)c->settings.solver_mode,
             (unsigned long long)(unsigned)c->settings.min_opt_iterations, a, b, th};
 }
 // Launch a captured sequence: replay g if it was captured under the current allocation

@@ -1,6 +1,11 @@
 """A/B whole library builds on the bench workload: each build runs in its own process
 (LDSO_BA_LIB=<path>), k_linearize / per-kernel HIP-event times, rounds interleaved.
-  python tools/ab_libs.py lib1.so lib2.so[:key=value,...] ... [--windows 64] [--rounds 3]"""
+  python tools/ab_libs.py lib1.so lib2.so[:key=value,...][+ENV=value,...][@tree] ... [--windows 64] [--rounds 3]
+key=value: set_tuning before the load; +ENV=value: environment of that build's processes (the
+library's switches); @tree: the checkout whose Python package drives the library (default: this
+one), for a build whose C ABI this checkout's bindings do not match.  The same library may be named
+twice (tell the entries apart with a +ENV of no effect, e.g. +AB=2): the spread between the two is
+the noise floor of the comparison."""
 import argparse
 import json
 import os
@@ -61,14 +66,20 @@ def main():
     res = {l: [] for l in a.libs}
     for _ in range(a.rounds):
         for l in a.libs:
-            path, _, tune = l.partition(":")  # lib.so:key=value,key=value -> set_tuning before load
+            spec, _, tree = l.partition("@")
+            spec, _, envs = spec.partition("+")
+            path, _, tune = spec.partition(":")  # lib.so:key=value,key=value -> set_tuning before load
             env = dict(os.environ, LDSO_BA_LIB=os.path.abspath(path), LDSO_AB_TUNE=tune)
-            p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+            env.update(kv.split("=", 1) for kv in filter(None, envs.split(",")))
+            child = code.replace(repr(ROOT), repr(os.path.abspath(tree))) if tree else code
+            p = subprocess.run([sys.executable, "-c", child], env=env, capture_output=True, text=True, timeout=300)
             line = [x for x in p.stdout.splitlines() if x.startswith("RESULT ")]
             if p.returncode != 0 or not line:
                 print(l, "FAILED", p.returncode, p.stderr[-2000:])
                 sys.exit(1)
             res[l].append(json.loads(line[0][7:]))
+            print(f"round {len(res[l])}: {l} k_stitch {res[l][-1]['acc']['k_stitch']:.2f} us, pass {res[l][-1]['wall']['pass']:.1f} us",
+                  file=sys.stderr, flush=True)
     for l, rs in res.items():
         best = {}
         for r in rs:
@@ -78,6 +89,8 @@ def main():
         print(l, " ".join(f"{m}:{k}={v:.1f}us" for (m, k), v in sorted(best.items())))
         print("   rounds acc:k_linearize", " ".join(f"{r['acc']['k_linearize']:.1f}" for r in rs),
               "noacc:k_linearize", " ".join(f"{r['noacc']['k_linearize']:.1f}" for r in rs))
+        print("   rounds acc:k_stitch", " ".join(f"{r['acc']['k_stitch']:.2f}" for r in rs),
+              "wall:pass", " ".join(f"{r['wall']['pass']:.1f}" for r in rs))
 
 
 if __name__ == "__main__":
