@@ -422,7 +422,7 @@ public:
     // (incremental edits, the loaded window tracked): then the read-back is deferred (see
     // setIncrementalEdits)
     void structuralTouch() {
-        if (incremental_ && mirrorTracked_ && resSync_ == ResSync::DeviceNewer) {
+        if (incremental_ && loaded_.tracked && resSync_ == ResSync::DeviceNewer) {
             deferred_ = true;
             return;
         }
@@ -456,19 +456,50 @@ public:
 
 private:
     enum class ResSync { Synced, HostNewer, DeviceNewer };
+    // The points and residuals of one ldso_ba_window as packed from the objects, and those objects.
+    // loaded_ is the window as it lies on the device; entries that left it since the load are null.
+    struct Mirror {
+        std::vector<int32_t> host, begin, target, rank;
+        bool ranked = true;  // every point carries its featureRank
+        std::vector<float> data, energy;
+        std::vector<int8_t> state;
+        std::vector<uint8_t> flags;
+        std::vector<PointFrameResidual *> res;
+        std::vector<PointHessian *> pts, resPoint;  // [P]; [R] the residual's point
+        std::vector<float> vals;  // [P][4] uploaded (idepth_scaled, idepth_zero_scaled, priorF, deltaF)
+        // incremental edits: the points by address (insertPoint takes an address out: it may be a new
+        // object's), the frameIDs of the window as loaded by id (empty: none is), and whether the
+        // mirror was built with the switch on (pointIndex is its)
+        std::unordered_map<const PointHessian *, int> pointIndex;
+        std::vector<int> loadedIds;
+        bool tracked = false;
+        void build(std::vector<PointHessian *> points);  // caller point order = the order given
+        void into(ldso_ba_window &w) const;
+        bool newEnergyDiffers() const;  // a residual's state_NewEnergy is not the state_energy packed
+    };
     bool upload();
+    bool uploadValues();
+    void buildMirror(const Mirror &old, bool sources, std::vector<int32_t> &pointSrc, std::vector<int32_t> &resSrc);
+    bool stageImages(std::vector<int64_t> &ids);
+    bool editWindow(const Mirror &old, ldso_ba_window &w, const std::vector<int64_t> &ids,
+                    const std::vector<int32_t> &pointSrc, const std::vector<int32_t> &resSrc);
+    void editApplied(const Mirror &old, const std::vector<int64_t> &ids, const std::vector<int32_t> &pointSrc);
+    bool reload(const ldso_ba_window &w, const std::vector<int64_t> &ids);
     void insertFrameImpl(shared_ptr<FrameHessian> fh, shared_ptr<CalibHessian> Hcalib, const ldso_ct_ctx *tracker);
     bool storeReserve();
     bool storePutHost(const FrameHessian &fh);
     bool storeHas(int frameID) const;
     bool uploadFrameTerms();
     bool runRelinearization();
-    bool readBack(bool points_and_th);
+    void syncInto(const Mirror &m);
+    bool readBack(const Mirror &m);
+    bool readPointsAndThresholds(const Mirror &m, bool thresholds);
     bool readPassSummary(bool fix);
     void fail(const char *what);
     void packFrames(std::vector<ldso_ba_frame_state> &fs) const;
     ldso_ba_ctx *ctx_ = nullptr;
     ldso_ba_ctx *margCtx_ = nullptr;
+    bool margContext();  // creates margCtx_ on first use
     std::vector<shared_ptr<PointHessian>> registry_;  // every inserted point not yet removed
     int device_ = 0;
     double currentLambda_ = 0;  // EnergyFunctional::currentLambda (set by solveSystemF)
@@ -476,17 +507,11 @@ private:
     CalibHessian calib_;
     bool dirty_ = true;
     std::string err_;
-    // SoA mirror (ldso_ba_window) of the loaded window
+    Mirror loaded_;
+    // the frame-level arrays of the loaded window (ldso_ba_window)
     std::vector<ldso_ba_frame_state> fs_;
-    std::vector<float> dI_, frameTH_, precalc_, pointData_, resEnergy_;
+    std::vector<float> dI_, frameTH_, precalc_;
     std::vector<double> adH_, adT_, cPrior_, fPrior_, fDelta_, fDeltaPrior_;
-    std::vector<int32_t> pointHost_, resBegin_, resTarget_, pointRank_;
-    bool pointRanked_ = false;
-    std::vector<int8_t> resState_;
-    std::vector<uint8_t> resFlags_;
-    std::vector<PointFrameResidual *> resPtr_;
-    std::vector<PointHessian *> ptPtr_, resPoint_;
-    std::vector<float> pointVals_;  // [P][4] uploaded (idepth_scaled, idepth_zero_scaled, priorF, deltaF)
     std::vector<ldso_ba_frame_state> fsUp_;  // frame states / calibration / thresholds last uploaded
     float calibUp_[4] = {0, 0, 0, 0};
     float cDeltaUp_[4] = {0, 0, 0, 0};  // cDeltaF as last uploaded (it feeds the bL prior)
@@ -494,28 +519,23 @@ private:
     int width_ = 0, height_ = 0;
     // frame store: resident_ selects the path; the store's size as reserved and the frameIDs in it
     bool resident_ = true;
-    // incremental edits: the frameIDs of the window as loaded by id (empty: none is), the loaded
-    // mirror's points by address (insertPoint takes an address out: it may be a new object's)
+    int storeW_ = 0, storeH_ = 0;
+    std::vector<int> storeIds_;
     bool incremental_ = false;
-    bool mirrorTracked_ = false;  // the loaded mirror was built with the switch on (mirrorPoint_ is its)
     bool deferred_ = false;       // structural changes are pending and the device is still newer
     long lostResultsAt_ = -1;     // passes_ at an edit that carried state the host never read
     double split_[6] = {0, 0, 0, 0, 0, 0};
     void forgetResidual(const PointFrameResidual *r) {  // r leaves the loaded mirror
         const int m = r->mirrorIdx;
-        if (incremental_ && m >= 0 && (size_t)m < resPtr_.size() && resPtr_[m] == r) resPtr_[m] = nullptr;
+        if (incremental_ && m >= 0 && (size_t)m < loaded_.res.size() && loaded_.res[m] == r) loaded_.res[m] = nullptr;
     }
     long editsApplied_ = 0, editsFallenBack_ = 0;
     bool deviceMarg_ = false;
     long deviceMargs_ = 0, readBacks_ = 0;
     bool marginalizeFromDevice();  // false: not possible here, take the host path
-    void frameTermsWindow(ldso_ba_window &w);
+    void frameTermsWindow(ldso_ba_window &w, bool hostImages = false);
     void applyMarginalization(const std::vector<PointFrameResidual *> &res, const std::vector<double> &H,
                               const std::vector<double> &b);
-    std::vector<int> loadedIds_;
-    std::unordered_map<const PointHessian *, int> mirrorPoint_;
-    int storeW_ = 0, storeH_ = 0;
-    std::vector<int> storeIds_;
     ResSync resSync_ = ResSync::Synced;
     long passes_ = 0;
     // the per-residual relinearisation (linearizeResidual): valid while epoch_ is unchanged and

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <utility>
 
 namespace ldso_amd {
 
@@ -29,63 +30,17 @@ void frame_state(const FrameHessian &F, ldso_ba_frame_state &S) {
     S.is_first_frame = F.frameID == 0 ? 1 : 0;
 }
 
-// points + residuals of one ldso_ba_window (caller point order = the order given)
-struct PointPack {
-    std::vector<int32_t> host, begin, target, rank;
-    bool ranked = true;  // every point carries its featureRank
-    std::vector<float> data, energy;
-    std::vector<int8_t> state;
-    std::vector<uint8_t> flags;
-    std::vector<PointFrameResidual *> res;
-    void build(const std::vector<PointHessian *> &pts) {
-        host.assign(pts.size(), 0);
-        rank.assign(pts.size(), 0);
-        ranked = true;
-        data.assign(pts.size() * LDSO_BA_POINT_STRIDE, 0.f);
-        begin.assign(pts.size() + 1, 0);
-        target.clear();
-        energy.clear();
-        state.clear();
-        flags.clear();
-        res.clear();
-        for (size_t q = 0; q < pts.size(); q++) {
-            const PointHessian &p = *pts[q];
-            host[q] = p.host.lock()->idx;
-            rank[q] = p.featureRank;
-            ranked = ranked && p.featureRank >= 0;
-            float *d = &data[q * LDSO_BA_POINT_STRIDE];
-            d[0] = p.u;
-            d[1] = p.v;
-            d[2] = p.idepth_scaled;
-            d[3] = p.idepth_zero_scaled;
-            d[4] = p.priorF;
-            d[5] = p.deltaF;
-            std::memcpy(d + 8, p.color, sizeof(p.color));
-            std::memcpy(d + 16, p.weights, sizeof(p.weights));
-            for (const shared_ptr<PointFrameResidual> &r : p.residuals) {
-                target.push_back(r->target.lock()->idx);
-                state.push_back((int8_t)r->state_state);
-                energy.push_back((float)r->state_energy);
-                flags.push_back((uint8_t)((r->isActiveAndIsGoodNEW ? LDSO_BA_FLAG_ACTIVE : 0u) |
-                                          (r->isNew ? LDSO_BA_FLAG_NEW : 0u)));
-                res.push_back(r.get());
-            }
-            begin[q + 1] = (int32_t)target.size();
-        }
-    }
-    void into(ldso_ba_window &w) {
-        w.n_points = (int32_t)host.size();
-        w.n_residuals = (int32_t)target.size();
-        w.point_host = host.data();
-        w.point_data = data.data();
-        w.point_res_begin = begin.data();
-        w.res_target = target.data();
-        w.res_state = state.data();
-        w.res_energy = energy.data();
-        w.res_flags = flags.data();
-        w.point_rank = ranked ? rank.data() : nullptr;
-    }
-};
+uint8_t res_flags(const PointFrameResidual &r) {
+    return (uint8_t)((r.isActiveAndIsGoodNEW ? LDSO_BA_FLAG_ACTIVE : 0u) | (r.isNew ? LDSO_BA_FLAG_NEW : 0u));
+}
+
+// the four values of a point that change from step to step (ldso_ba_update_points)
+void point_vals(const PointHessian &p, float v[4]) {
+    v[0] = p.idepth_scaled;
+    v[1] = p.idepth_zero_scaled;
+    v[2] = p.priorF;
+    v[3] = p.deltaF;
+}
 
 // write a device pass's per-residual results back into the residual objects
 bool read_residuals(ldso_ba_ctx *ctx, const std::vector<PointFrameResidual *> &res) {
@@ -117,6 +72,64 @@ bool read_residuals(ldso_ba_ctx *ctx, const std::vector<PointFrameResidual *> &r
 }
 
 }  // namespace
+
+void EnergyFunctional::Mirror::build(std::vector<PointHessian *> points) {
+    pts = std::move(points);
+    host.assign(pts.size(), 0);
+    rank.assign(pts.size(), 0);
+    ranked = true;
+    data.assign(pts.size() * LDSO_BA_POINT_STRIDE, 0.f);
+    vals.resize(4 * pts.size());
+    begin.assign(pts.size() + 1, 0);
+    target.clear();
+    energy.clear();
+    state.clear();
+    flags.clear();
+    res.clear();
+    resPoint.clear();
+    for (size_t q = 0; q < pts.size(); q++) {
+        const PointHessian &p = *pts[q];
+        host[q] = p.host.lock()->idx;
+        rank[q] = p.featureRank;
+        ranked = ranked && p.featureRank >= 0;
+        float *d = &data[q * LDSO_BA_POINT_STRIDE];
+        d[0] = p.u;
+        d[1] = p.v;
+        point_vals(p, d + 2);
+        point_vals(p, &vals[4 * q]);
+        std::memcpy(d + 8, p.color, sizeof(p.color));
+        std::memcpy(d + 16, p.weights, sizeof(p.weights));
+        for (const shared_ptr<PointFrameResidual> &r : p.residuals) {
+            target.push_back(r->target.lock()->idx);
+            state.push_back((int8_t)r->state_state);
+            energy.push_back((float)r->state_energy);
+            flags.push_back(res_flags(*r));
+            res.push_back(r.get());
+            resPoint.push_back(pts[q]);
+        }
+        begin[q + 1] = (int32_t)target.size();
+    }
+}
+
+void EnergyFunctional::Mirror::into(ldso_ba_window &w) const {
+    w.n_points = (int32_t)host.size();
+    w.n_residuals = (int32_t)target.size();
+    w.point_host = host.data();
+    w.point_data = data.data();
+    w.point_res_begin = begin.data();
+    w.res_target = target.data();
+    w.res_state = state.data();
+    w.res_energy = energy.data();
+    w.res_flags = flags.data();
+    w.point_rank = ranked ? rank.data() : nullptr;
+}
+
+// the device's state_NewEnergy is loaded equal to state_energy; the host's may differ
+bool EnergyFunctional::Mirror::newEnergyDiffers() const {
+    for (size_t k = 0; k < res.size(); k++)
+        if ((float)res[k]->state_NewEnergy != energy[k]) return true;
+    return false;
+}
 
 void FrameHessian::takeData(const ldso_ba_opt_settings *settings) {
     ldso_ba_frame_state S;
@@ -361,7 +374,7 @@ void EnergyFunctional::insertPoint(shared_ptr<PointHessian> ph) {
     structuralTouch();
     ph->status = PointStatus::ACTIVE;
     ph->alreadyRemoved = false;
-    mirrorPoint_.erase(ph.get());  // a new point, even at the address of one the mirror held
+    loaded_.pointIndex.erase(ph.get());  // a new point, even at the address of one the mirror held
     registry_.push_back(ph);
     allPoints.push_back(ph);
     nPoints++;
@@ -427,10 +440,10 @@ void EnergyFunctional::removePoint(shared_ptr<PointHessian> ph) {
         r->mirrorIdx = -1;
     }
     if (incremental_) {
-        const auto it = mirrorPoint_.find(ph.get());
-        if (it != mirrorPoint_.end()) {
-            if ((size_t)it->second < ptPtr_.size() && ptPtr_[it->second] == ph.get()) ptPtr_[it->second] = nullptr;
-            mirrorPoint_.erase(it);
+        const auto it = loaded_.pointIndex.find(ph.get());
+        if (it != loaded_.pointIndex.end()) {
+            if ((size_t)it->second < loaded_.pts.size() && loaded_.pts[it->second] == ph.get()) loaded_.pts[it->second] = nullptr;
+            loaded_.pointIndex.erase(it);
         }
     }
     ph->residuals.clear();
@@ -456,7 +469,7 @@ EnergyFunctional::FlagResult EnergyFunctional::flagPoints(const ldso_ba_flag_par
                "structural changes and residual edits that follow)";
         return out;
     }
-    const size_t P = ptPtr_.size(), R = resPtr_.size(), N = frames.size();
+    const size_t P = loaded_.pts.size(), R = loaded_.res.size(), N = frames.size();
     if (numGood.size() != P || lastRes.size() != 2 * P || (!lastState.empty() && lastState.size() != 2 * P) ||
         (!frameFlagged.empty() && frameFlagged.size() != N)) {
         err_ = "flagPoints: array sizes do not match the window (allPoints order: numGood [P], lastRes / lastState [2 P])";
@@ -475,19 +488,21 @@ EnergyFunctional::FlagResult EnergyFunctional::flagPoints(const ldso_ba_flag_par
         fail("ldso_ba_flag_points");
         return out;
     }
-    for (size_t q = 0; q < P; q++) ptPtr_[q]->status = (PointStatus)status[q];  // LDSO_BA_PT_* are PointStatus' values
+    for (size_t q = 0; q < P; q++) loaded_.pts[q]->status = (PointStatus)status[q];  // LDSO_BA_PT_* are PointStatus' values
     for (size_t k = 0; k < R; k++)
-        if (!live[k]) out.toRemove.push_back(resPtr_[k]);
+        if (!live[k]) out.toRemove.push_back(loaded_.res[k]);
     out.numGood.assign(ng.begin(), ng.end());
     for (int i = 0; i < 4; i++) out.counts[i] = counts[i];
     out.ok = true;
     return out;
 }
 
-// the frame-level fields of an ldso_ba_window, from the terms uploadFrameTerms computed last
-void EnergyFunctional::frameTermsWindow(ldso_ba_window &w) {
+// the frame-level fields of an ldso_ba_window, from the terms uploadFrameTerms computed last;
+// hostImages: with the images stageImages gathered for ldso_ba_load
+void EnergyFunctional::frameTermsWindow(ldso_ba_window &w, bool hostImages) {
     std::memset(&w, 0, sizeof(w));
     w.n_frames = nFrames;
+    if (hostImages) w.dI = dI_.data();
     w.width = width_;
     w.height = height_;
     std::memcpy(w.calib, calib_.value_scaledf, sizeof(w.calib));
@@ -525,41 +540,46 @@ void EnergyFunctional::applyMarginalization(const std::vector<PointFrameResidual
     makeIDX();
 }
 
-// marginalizePointsF from the loaded window's device arrays (setDeviceMarginalization).  Returns false
-// where that cannot give what the host path gives; true once the call is served (or failed: ok()).
-bool EnergyFunctional::marginalizeFromDevice() {
-    if (!ctx_ || !incremental_ || !resident_ || !mirrorTracked_ || resSync_ == ResSync::HostNewer) return false;
-    if ((int)loadedIds_.size() != nFrames) return false;
-    for (int f = 0; f < nFrames; f++)
-        if (loadedIds_[f] != frames[f]->frameID) return false;  // the loaded window has other frames
-    // current frame terms; without a structural change pending also the host's point values and residual edits
-    if (dirty_ ? !uploadFrameTerms() : !upload()) return true;
-    if (resSync_ == ResSync::HostNewer) return false;
-    const int R = (int)resPtr_.size();
-    std::vector<int32_t> pts;
-    std::vector<uint8_t> live((size_t)R, 0);
-    std::vector<PointFrameResidual *> res;
-    for (const shared_ptr<PointHessian> &p : allPointsToMarg) {
-        const auto it = mirrorPoint_.find(p.get());
-        if (it == mirrorPoint_.end() || (size_t)it->second >= ptPtr_.size() || ptPtr_[it->second] != p.get()) return false;
-        const int q = it->second;
-        const float pv[4] = {p->idepth_scaled, p->idepth_zero_scaled, p->priorF, p->deltaF};
-        if (std::memcmp(pv, &pointVals_[4 * (size_t)q], sizeof(pv)) != 0) return false;  // the device holds older values
-        int last = resBegin_[q] - 1;
-        for (const shared_ptr<PointFrameResidual> &r : p->residuals) {  // the loaded ones, in the loaded order
-            const int m = r->mirrorIdx;
-            if (m <= last || m >= resBegin_[q + 1] || resPtr_[m] != r.get()) return false;
-            live[m] = 1;
-            res.push_back(r.get());
-            last = m;
-        }
-        pts.push_back(q);
-    }
+bool EnergyFunctional::margContext() {
     if (!margCtx_ && ldso_ba_create(device_, &margCtx_)) {
         margCtx_ = nullptr;
         fail("ldso_ba_create (marginalisation)");
-        return true;
     }
+    return margCtx_ != nullptr;
+}
+
+// marginalizePointsF from the loaded window's device arrays (setDeviceMarginalization).  Returns false
+// where that cannot give what the host path gives; true once the call is served (or failed: ok()).
+bool EnergyFunctional::marginalizeFromDevice() {
+    const Mirror &m = loaded_;
+    if (!ctx_ || !incremental_ || !resident_ || !m.tracked || resSync_ == ResSync::HostNewer) return false;
+    if ((int)m.loadedIds.size() != nFrames) return false;
+    for (int f = 0; f < nFrames; f++)
+        if (m.loadedIds[f] != frames[f]->frameID) return false;  // the loaded window has other frames
+    // current frame terms; without a structural change pending also the host's point values and residual edits
+    if (dirty_ ? !uploadFrameTerms() : !upload()) return true;
+    if (resSync_ == ResSync::HostNewer) return false;
+    std::vector<int32_t> pts;
+    std::vector<uint8_t> live(m.res.size(), 0);
+    std::vector<PointFrameResidual *> res;
+    for (const shared_ptr<PointHessian> &p : allPointsToMarg) {
+        const auto it = m.pointIndex.find(p.get());
+        if (it == m.pointIndex.end() || (size_t)it->second >= m.pts.size() || m.pts[it->second] != p.get()) return false;
+        const int q = it->second;
+        float pv[4];
+        point_vals(*p, pv);
+        if (std::memcmp(pv, &m.vals[4 * (size_t)q], sizeof(pv)) != 0) return false;  // the device holds older values
+        int last = m.begin[q] - 1;
+        for (const shared_ptr<PointFrameResidual> &r : p->residuals) {  // the loaded ones, in the loaded order
+            const int k = r->mirrorIdx;
+            if (k <= last || k >= m.begin[q + 1] || m.res[k] != r.get()) return false;
+            live[k] = 1;
+            res.push_back(r.get());
+            last = k;
+        }
+        pts.push_back(q);
+    }
+    if (!margContext()) return true;
     ldso_ba_window w;
     frameTermsWindow(w);
     if (ldso_ba_load_marginalization_device(margCtx_, ctx_, 0, &w, (int32_t)pts.size(), pts.data(), live.data()))
@@ -589,15 +609,11 @@ void EnergyFunctional::marginalizePointsF() {
     residualTouched();
     if (allPointsToMarg.empty()) return;
     if (!upload()) return;  // current frame terms; the parent window lends its device images
-    if (!margCtx_ && ldso_ba_create(device_, &margCtx_)) {
-        margCtx_ = nullptr;
-        fail("ldso_ba_create (marginalisation)");
-        return;
-    }
+    if (!margContext()) return;
     // the parent window as loaded holds every point still flagged ACTIVE before this call
     std::vector<PointHessian *> pts;
     for (const shared_ptr<PointHessian> &p : allPointsToMarg) pts.push_back(p.get());
-    PointPack pk;
+    Mirror pk;
     pk.build(pts);
     ldso_ba_window w;
     frameTermsWindow(w);
@@ -734,21 +750,9 @@ bool EnergyFunctional::uploadFrameTerms() {
     }
     if (!dirty_) {  // structure unchanged: the frame terms alone (ldso_ba_update without point data)
         ldso_ba_window w;
-        std::memset(&w, 0, sizeof(w));
-        w.n_frames = N;
-        w.n_points = (int32_t)ptPtr_.size();
-        w.n_residuals = (int32_t)resPtr_.size();
-        w.width = width_;
-        w.height = height_;
-        std::memcpy(w.calib, calib_.value_scaledf, sizeof(w.calib));
-        w.frame_energy_th = frameTH_.data();
-        w.precalc = precalc_.data();
-        w.ad_host = adH_.data();
-        w.ad_target = adT_.data();
-        w.c_prior = cPrior_.data();
-        w.c_delta = cDeltaF;
-        w.frame_prior = fPrior_.data();
-        w.frame_delta_prior = fDeltaPrior_.data();
+        frameTermsWindow(w);
+        w.n_points = (int32_t)loaded_.pts.size();  // the loaded counts, no point arrays
+        w.n_residuals = (int32_t)loaded_.res.size();
         if (ldso_ba_update(ctx_, 0, &w)) {
             fail("ldso_ba_update");
             return false;
@@ -761,144 +765,80 @@ bool EnergyFunctional::uploadFrameTerms() {
     return true;
 }
 
-// The persistent SoA mirror of the window (ldso_ba_window).  A structural change (insert / drop /
-// remove / makeIDX / marginalisation) rebuilds and reloads it; otherwise only what changed goes
-// up: the frame terms, the points' four per-step values (ldso_ba_update_points, 16 B a point,
-// read through the mirror's raw pointers) and residual states edited on the host.
-bool EnergyFunctional::upload() {
-    if (!ctx_) return false;
-    const int N = nFrames;
-    if (N < 2) {
-        err_ = "need at least two frames";
+// Without a structural change only what changed goes up: the frame terms, the points' four per-step
+// values (ldso_ba_update_points, 16 B a point, read through the mirror's raw pointers) and residual
+// states edited on the host.
+bool EnergyFunctional::uploadValues() {
+    if (!uploadFrameTerms()) return false;
+    const size_t P = loaded_.pts.size(), R = loaded_.res.size();
+    std::vector<float> pv(4 * P);
+    for (size_t q = 0; q < P; q++) point_vals(*loaded_.pts[q], &pv[4 * q]);
+    if (P && std::memcmp(pv.data(), loaded_.vals.data(), pv.size() * sizeof(float)) != 0) {
+        if (ldso_ba_update_points(ctx_, 0, pv.data())) {
+            fail("ldso_ba_update_points");
+            return false;
+        }
+        loaded_.vals.swap(pv);
+    }
+    if (resSync_ != ResSync::HostNewer) return true;
+    std::vector<int8_t> st(R);
+    std::vector<float> se(R), ne(R);
+    std::vector<uint8_t> fl(R);
+    for (size_t k = 0; k < R; k++) {
+        const PointFrameResidual &r = *loaded_.res[k];
+        st[k] = (int8_t)r.state_state;
+        se[k] = (float)r.state_energy;
+        ne[k] = (float)r.state_NewEnergy;
+        fl[k] = res_flags(r);
+    }
+    if (ldso_ba_update_residuals(ctx_, 0, st.data(), se.data(), ne.data(), fl.data())) {
+        fail("ldso_ba_update_residuals");
         return false;
     }
-    if (!dirty_) {
-        if (!uploadFrameTerms()) return false;
-        const size_t P = ptPtr_.size();
-        std::vector<float> pv(4 * P);
-        for (size_t q = 0; q < P; q++) {
-            const PointHessian &p = *ptPtr_[q];
-            pv[4 * q] = p.idepth_scaled;
-            pv[4 * q + 1] = p.idepth_zero_scaled;
-            pv[4 * q + 2] = p.priorF;
-            pv[4 * q + 3] = p.deltaF;
-        }
-        if (P && std::memcmp(pv.data(), pointVals_.data(), pv.size() * sizeof(float)) != 0) {
-            if (ldso_ba_update_points(ctx_, 0, pv.data())) {
-                fail("ldso_ba_update_points");
-                return false;
-            }
-            pointVals_.swap(pv);
-        }
-        if (resSync_ == ResSync::HostNewer) {
-            const size_t R = resPtr_.size();
-            std::vector<int8_t> st(R);
-            std::vector<float> se(R), ne(R);
-            std::vector<uint8_t> fl(R);
-            for (size_t k = 0; k < R; k++) {
-                const PointFrameResidual &r = *resPtr_[k];
-                st[k] = (int8_t)r.state_state;
-                se[k] = (float)r.state_energy;
-                ne[k] = (float)r.state_NewEnergy;
-                fl[k] = (uint8_t)((r.isActiveAndIsGoodNEW ? LDSO_BA_FLAG_ACTIVE : 0u) | (r.isNew ? LDSO_BA_FLAG_NEW : 0u));
-            }
-            if (ldso_ba_update_residuals(ctx_, 0, st.data(), se.data(), ne.data(), fl.data())) {
-                fail("ldso_ba_update_residuals");
-                return false;
-            }
-            resSync_ = ResSync::Synced;
-        }
-        return true;
-    }
-    // structural change: rebuild the mirror (the only place the weak_ptr graph is walked)
-    using SplitClock = std::chrono::steady_clock;
-    auto ms_since = [](SplitClock::time_point t) { return std::chrono::duration<double, std::milli>(SplitClock::now() - t).count(); };
-    SplitClock::time_point t_part = SplitClock::now();
-    // incremental edits: an edit can be tried if the loaded window's entries were tracked
-    bool tryEdit = incremental_ && resident_ && mirrorTracked_ && !loadedIds_.empty();
-    if (deferred_ && !tryEdit) syncResiduals();  // the reload below sends the host's values: make them current
-    if (!uploadFrameTerms()) return false;
-    split_[3] += ms_since(t_part);
-    t_part = SplitClock::now();
-    // the loaded mirror's entries, compared by address and never dereferenced (dropped ones are null)
-    std::vector<PointFrameResidual *> oldRes;
-    std::vector<PointHessian *> oldPt;
-    std::vector<float> oldVals;
-    if (tryEdit) {
-        oldRes = resPtr_;
-        oldPt = ptPtr_;
-        oldVals = pointVals_;
-    }
-    ptPtr_.clear();
-    for (const shared_ptr<PointHessian> &p : allPoints) ptPtr_.push_back(p.get());
-    PointPack pk;
-    pk.build(ptPtr_);
-    // where every entry of the new mirror lies in the loaded one (-1: new).  A residual keeps its
-    // mirrorIdx until it is inserted or dropped; a point is found by address.
-    std::vector<int32_t> pointSrc, resSrc;
-    if (tryEdit) {
-        pointSrc.assign(ptPtr_.size(), -1);
-        resSrc.assign(pk.res.size(), -1);
-        for (size_t q = 0; q < ptPtr_.size(); q++) {
-            const auto it = mirrorPoint_.find(ptPtr_[q]);
-            if (it != mirrorPoint_.end()) pointSrc[q] = it->second;
+    resSync_ = ResSync::Synced;
+    return true;
+}
+
+// loaded_ becomes the mirror of the window as the objects have it now (the only place the weak_ptr
+// graph is walked).  sources: also where every entry lies in `old`, the mirror loaded so far (-1: new);
+// a residual keeps its mirrorIdx until it is inserted or dropped, a point is found by address.  old's
+// entries are compared by address and never dereferenced (dropped ones are null).
+void EnergyFunctional::buildMirror(const Mirror &old, bool sources, std::vector<int32_t> &pointSrc,
+                                   std::vector<int32_t> &resSrc) {
+    std::vector<PointHessian *> pts;
+    for (const shared_ptr<PointHessian> &p : allPoints) pts.push_back(p.get());
+    Mirror &m = loaded_;
+    m = Mirror();
+    m.build(pts);
+    if (sources) {
+        pointSrc.assign(m.pts.size(), -1);
+        resSrc.assign(m.res.size(), -1);
+        for (size_t q = 0; q < m.pts.size(); q++) {
+            const auto it = old.pointIndex.find(m.pts[q]);
+            if (it != old.pointIndex.end()) pointSrc[q] = it->second;
         }
         bool new_ne_differs = false;
-        for (size_t k = 0; k < pk.res.size(); k++) {
-            const int m = pk.res[k]->mirrorIdx;
-            if (m >= 0 && (size_t)m < oldRes.size() && oldRes[m] == pk.res[k]) resSrc[k] = m;
-            else new_ne_differs = new_ne_differs || (float)pk.res[k]->state_NewEnergy != pk.energy[k];
+        for (size_t k = 0; k < m.res.size(); k++) {
+            const int o = m.res[k]->mirrorIdx;
+            if (o >= 0 && (size_t)o < old.res.size() && old.res[o] == m.res[k]) resSrc[k] = o;
+            else new_ne_differs = new_ne_differs || (float)m.res[k]->state_NewEnergy != m.energy[k];
         }
         // a deferred read-back stays deferred through the edit only if the new residuals need no
         // upload of their own afterwards (state_NewEnergy is loaded equal to state_energy)
         if (deferred_ && new_ne_differs) {
-            resPtr_.swap(oldRes);
-            ptPtr_.swap(oldPt);
-            syncResiduals();  // reads the loaded window into the loaded mirror's objects
-            resPtr_.swap(oldRes);
-            ptPtr_.swap(oldPt);
-            pk.build(ptPtr_);
+            syncInto(old);  // reads the loaded window into the loaded mirror's objects
+            m.build(pts);
         }
     }
-    auto adopt_pack = [&]() {
-        pointHost_ = pk.host;
-        pointRank_ = pk.rank;
-        pointRanked_ = pk.ranked;
-        pointData_ = pk.data;
-        resBegin_ = pk.begin;
-        resTarget_ = pk.target;
-        resState_ = pk.state;
-        resEnergy_ = pk.energy;
-        resFlags_ = pk.flags;
-    };
-    adopt_pack();
-    resPtr_ = pk.res;
-    nResiduals = (int)resPtr_.size();
-    resPoint_.resize(resPtr_.size());
-    for (size_t q = 0; q < ptPtr_.size(); q++)
-        for (int k = resBegin_[q]; k < resBegin_[q + 1]; k++) {
-            resPtr_[k]->mirrorIdx = k;
-            resPoint_[k] = ptPtr_[q];
-        }
-    pointVals_.resize(4 * ptPtr_.size());
-    for (size_t q = 0; q < ptPtr_.size(); q++) {
-        pointVals_[4 * q] = pointData_[q * LDSO_BA_POINT_STRIDE + 2];
-        pointVals_[4 * q + 1] = pointData_[q * LDSO_BA_POINT_STRIDE + 3];
-        pointVals_[4 * q + 2] = pointData_[q * LDSO_BA_POINT_STRIDE + 4];
-        pointVals_[4 * q + 3] = pointData_[q * LDSO_BA_POINT_STRIDE + 5];
-    }
-    ldso_ba_window w;
-    std::memset(&w, 0, sizeof(w));
-    w.n_frames = N;
-    w.n_points = (int32_t)pointHost_.size();
-    w.n_residuals = nResiduals;
-    w.width = width_;
-    w.height = height_;
-    std::memcpy(w.calib, calib_.value_scaledf, sizeof(w.calib));
-    // the images: by frame id out of the store (frames missing there -- the path was switched on
-    // with the window in place, or the store was reserved again -- go in now from their host dI), or
-    // gathered on the host for ldso_ba_load
-    std::vector<int64_t> ids;
+    nResiduals = (int)m.res.size();
+    for (size_t k = 0; k < m.res.size(); k++) m.res[k]->mirrorIdx = (int)k;
+}
+
+// The window's images: by frame id out of the store (frames missing there -- the path was switched on
+// with the window in place, or the store was reserved again -- go in now from their host dI), or
+// gathered on the host into dI_ for ldso_ba_load
+bool EnergyFunctional::stageImages(std::vector<int64_t> &ids) {
+    const int N = nFrames;
     if (resident_) {
         if (!storeReserve()) return false;
         for (int f = 0; f < N && resident_; f++)
@@ -907,121 +847,122 @@ bool EnergyFunctional::upload() {
     if (resident_) {
         for (int f = 0; f < N; f++) ids.push_back(frames[f]->frameID);
         std::vector<float>().swap(dI_);
-    } else {
-        dI_.resize((size_t)N * width_ * height_ * 3);
-        for (int f = 0; f < N; f++) {
-            if (!frames[f]->dI) {
-                err_ = "frame " + std::to_string(frames[f]->frameID) + " has no host dI (handed over from the tracker): ldso_ba_load needs it";
-                return false;
-            }
-            std::memcpy(&dI_[(size_t)f * width_ * height_ * 3], frames[f]->dI, (size_t)width_ * height_ * 3 * sizeof(float));
-        }
-        w.dI = dI_.data();
+        return true;
     }
-    w.frame_energy_th = frameTH_.data();
-    w.precalc = precalc_.data();
-    w.ad_host = adH_.data();
-    w.ad_target = adT_.data();
-    w.c_prior = cPrior_.data();
-    w.c_delta = cDeltaF;
-    w.frame_prior = fPrior_.data();
-    w.frame_delta_prior = fDeltaPrior_.data();
-    w.point_host = pointHost_.data();
-    w.point_data = pointData_.data();
-    w.point_res_begin = resBegin_.data();
-    w.res_target = resTarget_.data();
-    w.res_state = resState_.data();
-    w.res_energy = resEnergy_.data();
-    w.res_flags = resFlags_.data();
-    w.point_rank = pointRanked_ ? pointRank_.data() : nullptr;
-    mirrorTracked_ = incremental_ && resident_;
-    if (mirrorTracked_) {
-        mirrorPoint_.clear();
-        for (size_t q = 0; q < ptPtr_.size(); q++) mirrorPoint_[ptPtr_[q]] = (int)q;
+    const size_t px = (size_t)width_ * height_ * 3;
+    dI_.resize(N * px);
+    for (int f = 0; f < N; f++) {
+        if (!frames[f]->dI) {
+            err_ = "frame " + std::to_string(frames[f]->frameID) + " has no host dI (handed over from the tracker): ldso_ba_load needs it";
+            return false;
+        }
+        std::memcpy(&dI_[f * px], frames[f]->dI, px * sizeof(float));
     }
-    split_[0] += 1;
-    split_[2] += ms_since(t_part);
-    t_part = SplitClock::now();
-    if (tryEdit && resident_) {
-        std::vector<int32_t> frameSrc(N, -1);
-        for (int f = 0; f < N; f++) {
-            const auto it = std::find(loadedIds_.begin(), loadedIds_.end(), frames[f]->frameID);
-            if (it != loadedIds_.end()) frameSrc[f] = (int32_t)(it - loadedIds_.begin());
-        }
-        const ldso_ba_edit ed = {&w, ids.data(), frameSrc.data(), pointSrc.data(), resSrc.data()};
-        if (ldso_ba_edit_window(ctx_, 0, &ed) == 0) {
-            split_[4] += ms_since(t_part);
-            t_part = SplitClock::now();
-            editsApplied_++;
-            loadedIds_.assign(ids.begin(), ids.end());
-            // the device holds, on a surviving point, the values it held before: the branch above
-            // sends the points' values if the host's differ
-            for (size_t q = 0; q < ptPtr_.size(); q++)
-                if (pointSrc[q] >= 0 && (size_t)4 * pointSrc[q] + 3 < oldVals.size())
-                    std::memcpy(&pointVals_[4 * q], &oldVals[4 * (size_t)pointSrc[q]], 4 * sizeof(float));
-            if (deferred_) {
-                // the surviving residuals' state never came to the host and went into the new window
-                // on the device; the last pass's results are gone, as after a load
-                deferred_ = false;
-                lostResultsAt_ = passes_;
-                outStatePass_ = outCenterPass_ = -1;  // cached in the loaded mirror's order
-                outState_.assign(resPtr_.size(), 0);
-            } else {
-                // ... and on a surviving residual the state the host read back (or edited since:
-                // HostNewer, sent by the branch above)
-                bool ne_differs = false;
-                for (size_t k = 0; k < resPtr_.size() && !ne_differs; k++)
-                    ne_differs = (float)resPtr_[k]->state_NewEnergy != resEnergy_[k];
-                if (ne_differs) resSync_ = ResSync::HostNewer;
-            }
-            dirty_ = false;
-            const bool done = upload();
-            split_[5] += ms_since(t_part);
-            return done;
-        }
-        editsFallenBack_++;  // refused (ldso_ba_last_error says why): the reload below
-        if (deferred_) {  // the loaded window is untouched: read it into the loaded mirror's objects first
-            std::vector<PointFrameResidual *> newRes = resPtr_;
-            std::vector<PointHessian *> newPt = ptPtr_;
-            resPtr_ = oldRes;
-            ptPtr_ = oldPt;
-            syncResiduals();
-            resPtr_ = newRes;
-            ptPtr_ = newPt;
-            pk.build(ptPtr_);
-            adopt_pack();
-            w.point_host = pointHost_.data();
-            w.point_data = pointData_.data();
-            w.point_res_begin = resBegin_.data();
-            w.res_target = resTarget_.data();
-            w.res_state = resState_.data();
-            w.res_energy = resEnergy_.data();
-            w.res_flags = resFlags_.data();
-            w.point_rank = pointRanked_ ? pointRank_.data() : nullptr;
-        }
+    return true;
+}
+
+// ldso_ba_edit_window from `old`, the mirror of the window on the device, to loaded_.  False: refused
+// (ldso_ba_last_error says why), the device's window is untouched and w current for the reload.
+bool EnergyFunctional::editWindow(const Mirror &old, ldso_ba_window &w, const std::vector<int64_t> &ids,
+                                  const std::vector<int32_t> &pointSrc, const std::vector<int32_t> &resSrc) {
+    std::vector<int32_t> frameSrc(nFrames, -1);
+    for (int f = 0; f < nFrames; f++) {
+        const auto it = std::find(old.loadedIds.begin(), old.loadedIds.end(), frames[f]->frameID);
+        if (it != old.loadedIds.end()) frameSrc[f] = (int32_t)(it - old.loadedIds.begin());
     }
-    loadedIds_.clear();
+    const ldso_ba_edit ed = {&w, ids.data(), frameSrc.data(), pointSrc.data(), resSrc.data()};
+    if (ldso_ba_edit_window(ctx_, 0, &ed) == 0) return true;
+    editsFallenBack_++;
+    if (deferred_) {  // read the loaded window into the loaded mirror's objects first
+        syncInto(old);
+        loaded_.build(loaded_.pts);
+        loaded_.into(w);
+    }
+    return false;
+}
+
+// the edit went through: loaded_ is the device's window
+void EnergyFunctional::editApplied(const Mirror &old, const std::vector<int64_t> &ids, const std::vector<int32_t> &pointSrc) {
+    Mirror &m = loaded_;
+    editsApplied_++;
+    m.loadedIds.assign(ids.begin(), ids.end());
+    // the device holds, on a surviving point, the values it held before: uploadValues sends the
+    // points' values if the host's differ
+    for (size_t q = 0; q < m.pts.size(); q++)
+        if (pointSrc[q] >= 0 && (size_t)4 * pointSrc[q] + 3 < old.vals.size())
+            std::memcpy(&m.vals[4 * q], &old.vals[4 * (size_t)pointSrc[q]], 4 * sizeof(float));
+    if (deferred_) {
+        // the surviving residuals' state never came to the host and went into the new window
+        // on the device; the last pass's results are gone, as after a load
+        deferred_ = false;
+        lostResultsAt_ = passes_;
+        outStatePass_ = outCenterPass_ = -1;  // cached in the loaded mirror's order
+        outState_.assign(m.res.size(), 0);
+    } else if (m.newEnergyDiffers()) {
+        // ... and on a surviving residual the state the host read back (or edited since: HostNewer,
+        // sent by uploadValues)
+        resSync_ = ResSync::HostNewer;
+    }
+    dirty_ = false;
+}
+
+bool EnergyFunctional::reload(const ldso_ba_window &w, const std::vector<int64_t> &ids) {
     deferred_ = false;
     lostResultsAt_ = -1;
     if (resident_ ? ldso_ba_load_frames(ctx_, 1, &w, ids.data(), 0, 1) : ldso_ba_load(ctx_, 1, &w, 0, 1)) {
         fail(resident_ ? "ldso_ba_load_frames" : "ldso_ba_load");
         return false;
     }
-    if (resident_) loadedIds_.assign(ids.begin(), ids.end());
-    // the device's state_NewEnergy starts as state_energy (ldso_ba_load); the host's may differ
-    bool ne_differs = false;
-    for (size_t k = 0; k < resPtr_.size() && !ne_differs; k++)
-        ne_differs = (float)resPtr_[k]->state_NewEnergy != resEnergy_[k];
-    resSync_ = ne_differs ? ResSync::HostNewer : ResSync::Synced;
+    if (resident_) loaded_.loadedIds.assign(ids.begin(), ids.end());
+    resSync_ = loaded_.newEnergyDiffers() ? ResSync::HostNewer : ResSync::Synced;
     dirty_ = false;
-    split_[4] += ms_since(t_part);
-    if (resSync_ == ResSync::HostNewer) {
-        t_part = SplitClock::now();
-        const bool done = upload();
-        split_[5] += ms_since(t_part);
-        return done;
-    }
     return true;
+}
+
+// The persistent SoA mirror of the window (ldso_ba_window), loaded_.  A structural change (insert /
+// drop / remove / makeIDX / marginalisation) rebuilds it and edits or reloads the device's window;
+// otherwise only what changed goes up (uploadValues).
+bool EnergyFunctional::upload() {
+    if (!ctx_) return false;
+    if (nFrames < 2) {
+        err_ = "need at least two frames";
+        return false;
+    }
+    if (!dirty_) return uploadValues();
+    using SplitClock = std::chrono::steady_clock;
+    auto ms_since = [](SplitClock::time_point t) { return std::chrono::duration<double, std::milli>(SplitClock::now() - t).count(); };
+    SplitClock::time_point t_part = SplitClock::now();
+    // incremental edits: an edit can be tried if the loaded window's entries were tracked
+    const bool tryEdit = incremental_ && resident_ && loaded_.tracked && !loaded_.loadedIds.empty();
+    if (deferred_ && !tryEdit) syncResiduals();  // the reload below sends the host's values: make them current
+    if (!uploadFrameTerms()) return false;
+    split_[3] += ms_since(t_part);
+    t_part = SplitClock::now();
+    const Mirror old = std::move(loaded_);
+    std::vector<int32_t> pointSrc, resSrc;
+    buildMirror(old, tryEdit, pointSrc, resSrc);
+    std::vector<int64_t> ids;
+    if (!stageImages(ids)) return false;
+    ldso_ba_window w;
+    frameTermsWindow(w, !resident_);
+    loaded_.into(w);
+    loaded_.tracked = incremental_ && resident_;
+    if (loaded_.tracked) {
+        loaded_.pointIndex.reserve(loaded_.pts.size());
+        for (size_t q = 0; q < loaded_.pts.size(); q++) loaded_.pointIndex[loaded_.pts[q]] = (int)q;
+    }
+    split_[0] += 1;
+    split_[2] += ms_since(t_part);
+    t_part = SplitClock::now();
+    const bool edited = tryEdit && resident_ && editWindow(old, w, ids, pointSrc, resSrc);
+    if (!edited && !reload(w, ids)) return false;
+    split_[4] += ms_since(t_part);
+    t_part = SplitClock::now();
+    if (edited) editApplied(old, ids, pointSrc);
+    if (!edited && resSync_ != ResSync::HostNewer) return true;
+    const bool done = uploadValues();  // what the host changed on a surviving entry follows
+    split_[5] += ms_since(t_part);
+    return done;
 }
 
 void EnergyFunctional::resetOOB() {
@@ -1041,12 +982,37 @@ void EnergyFunctional::resetOOB() {
     }
 }
 
-// every per-residual / per-point result of the device's last pass into the objects
-bool EnergyFunctional::readBack(bool points_and_th) {
+// the points' HdiF / bdSumF / idepth_hessian of the device's last pass into m's points and, with
+// `thresholds`, the frames' energy thresholds into the frames
+bool EnergyFunctional::readPointsAndThresholds(const Mirror &m, bool thresholds) {
+    const size_t P = m.pts.size();
+    std::vector<float> hdi(P), bds(P), ih(P);
+    if (P && ldso_ba_get_points(ctx_, 0, hdi.data(), bds.data(), ih.data(), nullptr, nullptr, nullptr)) {
+        fail("ldso_ba_get_points");
+        return false;
+    }
+    for (size_t q = 0; q < P; q++) {
+        if (!m.pts[q]) continue;  // removed since the load (a deferred read-back)
+        m.pts[q]->HdiF = hdi[q];
+        m.pts[q]->bdSumF = bds[q];
+        m.pts[q]->idepth_hessian = ih[q];
+    }
+    std::vector<float> th(nFrames);
+    if (thresholds && ldso_ba_get_frame_energy_th(ctx_, 0, th.data()) == 0) {
+        for (int f = 0; f < nFrames; f++) frames[f]->frameEnergyTH = th[f];
+        thUp_ = th;  // the device holds these already
+        frameTH_ = th;
+    }
+    return true;
+}
+
+// every per-residual / per-point result of the device's last pass into the objects of m, the mirror
+// of the window the device holds
+bool EnergyFunctional::readBack(const Mirror &m) {
     if (lostResultsAt_ == passes_) {
         // an edit carried the residuals' state past the host and reset the last pass's results, as a
         // load does: state, energy and flags are what the device still knows
-        const size_t R = resPtr_.size();
+        const size_t R = m.res.size();
         std::vector<int8_t> st(R);
         std::vector<float> se(R);
         std::vector<uint8_t> fl(R);
@@ -1055,8 +1021,8 @@ bool EnergyFunctional::readBack(bool points_and_th) {
             return false;
         }
         for (size_t k = 0; k < R; k++) {
-            if (!resPtr_[k]) continue;
-            PointFrameResidual &r = *resPtr_[k];
+            if (!m.res[k]) continue;
+            PointFrameResidual &r = *m.res[k];
             r.state_state = (ResState)st[k];
             r.state_energy = r.state_NewEnergy = se[k];
             r.isActiveAndIsGoodNEW = (fl[k] & LDSO_BA_FLAG_ACTIVE) != 0;
@@ -1064,33 +1030,13 @@ bool EnergyFunctional::readBack(bool points_and_th) {
         resSync_ = ResSync::Synced;
         return true;
     }
-    if (!read_residuals(ctx_, resPtr_)) {
+    if (!read_residuals(ctx_, m.res)) {
         fail("ldso_ba_get_residuals");
         return false;
     }
     resSync_ = ResSync::Synced;
-    if (!points_and_th) return true;
-    const int P = (int)ptPtr_.size();
-    std::vector<float> hdi(P), bds(P), ih(P);
-    if (P && ldso_ba_get_points(ctx_, 0, hdi.data(), bds.data(), ih.data(), nullptr, nullptr, nullptr)) {
-        fail("ldso_ba_get_points");
-        return false;
-    }
-    for (int q = 0; q < P; q++) {
-        if (!ptPtr_[q]) continue;  // removed since the load (a deferred read-back)
-        ptPtr_[q]->HdiF = hdi[q];
-        ptPtr_[q]->bdSumF = bds[q];
-        ptPtr_[q]->idepth_hessian = ih[q];
-    }
-    if (dirty_) return true;  // the frames may have changed since the load: their thresholds were read with the pass
-    const int N = nFrames;
-    std::vector<float> th(N);
-    if (ldso_ba_get_frame_energy_th(ctx_, 0, th.data()) == 0) {
-        for (int f = 0; f < N; f++) frames[f]->frameEnergyTH = th[f];
-        thUp_ = th;  // the device holds these already
-        frameTH_ = th;
-    }
-    return true;
+    // the frames may have changed since the load (dirty_): their thresholds were read with the pass
+    return readPointsAndThresholds(m, !dirty_);
 }
 
 // linearizeAll's read-back of what its callers need at once: the frame thresholds, the points'
@@ -1098,7 +1044,8 @@ bool EnergyFunctional::readBack(bool points_and_th) {
 // flags and relBS; every other residual field stays on the device until a consumer asks
 // (syncResiduals, a residual method, residualCenter)
 bool EnergyFunctional::readPassSummary(bool fix) {
-    const size_t R = resPtr_.size(), P = ptPtr_.size();
+    const Mirror &m = loaded_;
+    const size_t R = m.res.size(), P = m.pts.size();
     const int N = nFrames;
     std::vector<uint8_t> fl(R);
     std::vector<float> rb(fix ? R : 0);
@@ -1109,32 +1056,18 @@ bool EnergyFunctional::readPassSummary(bool fix) {
         return false;
     }
     outStatePass_ = passes_;
-    std::vector<float> hdi(P), bds(P), ih(P), th(N);
-    if (P && ldso_ba_get_points(ctx_, 0, hdi.data(), bds.data(), ih.data(), nullptr, nullptr, nullptr)) {
-        fail("ldso_ba_get_points");
-        return false;
-    }
-    for (size_t q = 0; q < P; q++) {
-        ptPtr_[q]->HdiF = hdi[q];
-        ptPtr_[q]->bdSumF = bds[q];
-        ptPtr_[q]->idepth_hessian = ih[q];
-    }
-    if (ldso_ba_get_frame_energy_th(ctx_, 0, th.data()) == 0) {
-        for (int f = 0; f < N; f++) frames[f]->frameEnergyTH = th[f];
-        thUp_ = th;  // the device holds these already
-        frameTH_ = th;
-    }
+    if (!readPointsAndThresholds(m, true)) return false;
     if (fix) {
         fix_.toRemove.clear();
         fix_.maxRelBS.assign(P, 0.f);
         fix_.numGood.assign(P, 0);
         fix_.lastState.assign(2 * P, -1);
         for (size_t q = 0; q < P; q++)
-            for (int k = resBegin_[q]; k < resBegin_[q + 1]; k++) {
-                const int t = resTarget_[k];
+            for (int k = m.begin[q]; k < m.begin[q + 1]; k++) {
+                const int t = m.target[k];
                 if (t >= N - 2) fix_.lastState[2 * q + (N - 1 - t)] = outState_[k];
                 if (!(fl[k] & LDSO_BA_FLAG_ACTIVE)) {
-                    fix_.toRemove.push_back(resPtr_[k]);
+                    fix_.toRemove.push_back(m.res[k]);
                 } else if (fl[k] & LDSO_BA_FLAG_NEW) {  // FullSystem.cc:1799-1813
                     fix_.maxRelBS[q] = std::max(fix_.maxRelBS[q], rb[k]);
                     fix_.numGood[q]++;
@@ -1150,19 +1083,19 @@ ResState EnergyFunctional::residualState(int k) {
                                                                       nullptr, nullptr, nullptr, nullptr, nullptr) == 0)
             outStatePass_ = passes_;
         else
-            return resPtr_[k]->state_state;  // the host copy is current
+            return loaded_.res[k]->state_state;  // the host copy is current
     }
     return (ResState)outState_[k];
 }
 
 const float *EnergyFunctional::residualCenter(int k) {
-    if (resSync_ != ResSync::DeviceNewer) return resPtr_[k]->centerProjectedTo;  // the host copy is current
+    if (resSync_ != ResSync::DeviceNewer) return loaded_.res[k]->centerProjectedTo;  // the host copy is current
     if (outCenterPass_ != passes_) {
-        outCenter_.resize(3 * resPtr_.size());
+        outCenter_.resize(3 * loaded_.res.size());
         if (ldso_ba_get_residuals(ctx_, 0, nullptr, nullptr, nullptr, nullptr, outCenter_.data(), nullptr, nullptr,
                                   nullptr)) {
             fail("ldso_ba_get_residuals");
-            return resPtr_[k]->centerProjectedTo;
+            return loaded_.res[k]->centerProjectedTo;
         }
         outCenterPass_ = passes_;
     }
@@ -1187,7 +1120,10 @@ bool EnergyFunctional::setCoarseTrackingRef(ldso_ct_ctx *tracker, const ldso_ct_
     return ok();
 }
 
-void EnergyFunctional::syncResiduals() {
+void EnergyFunctional::syncResiduals() { syncInto(loaded_); }
+
+// m: the mirror of the window the device holds
+void EnergyFunctional::syncInto(const Mirror &m) {
     // after a structural change the device's window is no longer the mirror's, unless the read-back
     // was deferred for an edit (structuralTouch): then the loaded window is still there to read
     if (resSync_ != ResSync::DeviceNewer || !ctx_ || (dirty_ && !deferred_)) return;
@@ -1195,7 +1131,7 @@ void EnergyFunctional::syncResiduals() {
     deferred_ = false;
     const auto t0 = std::chrono::steady_clock::now();
     readBacks_++;
-    readBack(true);
+    readBack(m);
     split_[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
@@ -1224,7 +1160,7 @@ Vec3 EnergyFunctional::linearizeAll(bool fixLinearization) {
 // resetOOB; the entries serve PointFrameResidual::linearize until the next change of the window
 bool EnergyFunctional::runRelinearization() {
     if (!upload()) return false;
-    const size_t R = resPtr_.size();
+    const size_t R = loaded_.res.size();
     cNewState_.assign(R, 0);
     cCenterOk_.assign(R, 0);
     cNewEnergy_.assign(R, 0.f);
@@ -1239,7 +1175,7 @@ bool EnergyFunctional::runRelinearization() {
     passes_++;
     cSnap_.resize(4 * R);
     for (size_t k = 0; k < R; k++) {
-        const PointHessian &p = *resPoint_[k];
+        const PointHessian &p = *loaded_.resPoint[k];
         cSnap_[4 * k] = p.u;
         cSnap_[4 * k + 1] = p.v;
         cSnap_[4 * k + 2] = p.idepth_scaled;
@@ -1252,9 +1188,9 @@ bool EnergyFunctional::runRelinearization() {
 double EnergyFunctional::linearizeResidual(PointFrameResidual &r) {
     auto fresh = [&]() {
         if (dirty_ || cacheEpoch_ != epoch_ || r.mirrorIdx < 0 || (size_t)r.mirrorIdx >= cNewState_.size() ||
-            resPtr_[r.mirrorIdx] != &r)
+            loaded_.res[r.mirrorIdx] != &r)
             return false;
-        const PointHessian &p = *resPoint_[r.mirrorIdx];
+        const PointHessian &p = *loaded_.resPoint[r.mirrorIdx];
         const float *sn = &cSnap_[4 * (size_t)r.mirrorIdx];
         if (!(sn[0] == p.u && sn[1] == p.v && sn[2] == p.idepth_scaled && sn[3] == p.idepth_zero_scaled)) return false;
         // the frame terms the pass used: the residual's host and target as uploaded (state,
@@ -1298,7 +1234,8 @@ Vec3 EnergyFunctional::optimize(int n_its, shared_ptr<CalibHessian> HCalib, std:
     epoch_++;
     calib_ = *HCalib;
     if (!upload()) return out;
-    const int N = nFrames, n = 8 * N + CPARS, P = (int)ptPtr_.size();
+    const std::vector<PointHessian *> &pts = loaded_.pts;
+    const int N = nFrames, n = 8 * N + CPARS, P = (int)pts.size();
     std::vector<double> ns((size_t)7 * n), e((size_t)3 * (n_its + 1));
     if (ldso_ba_nullspaces(N, fs_.data(), ns.data())) {
         fail("ldso_ba_nullspaces");
@@ -1324,8 +1261,8 @@ Vec3 EnergyFunctional::optimize(int n_its, shared_ptr<CalibHessian> HCalib, std:
     HCalib->setValue(calib_out);
     calib_ = *HCalib;
     for (int q = 0; q < P; q++) {
-        ptPtr_[q]->setIdepth(idepth[q]);
-        ptPtr_[q]->setIdepthZero(idepth[q]);
+        pts[q]->setIdepth(idepth[q]);
+        pts[q]->setIdepthZero(idepth[q]);
     }
     // setNewFrameEnergyTH of the loop's passes (the device holds it; the next frame-term upload
     // must not overwrite it with the old value)
@@ -1340,9 +1277,9 @@ Vec3 EnergyFunctional::optimize(int n_its, shared_ptr<CalibHessian> HCalib, std:
     // takeData of the stepped states (the reference's setPrecalcValues), which differ from the
     // device's in libm's last ulp; upload() re-sends them in one staged launch.
     for (int q = 0; q < P; q++) {
-        pointVals_[4 * q] = ptPtr_[q]->idepth_scaled;
-        pointVals_[4 * q + 1] = ptPtr_[q]->idepth_zero_scaled;
-        pointVals_[4 * q + 3] = ptPtr_[q]->deltaF;
+        loaded_.vals[4 * q] = pts[q]->idepth_scaled;
+        loaded_.vals[4 * q + 1] = pts[q]->idepth_zero_scaled;
+        loaded_.vals[4 * q + 3] = pts[q]->deltaF;
     }
     resSync_ = ResSync::DeviceNewer;
     resInA = (int)e[3 * n_its + 2];
@@ -1401,12 +1338,12 @@ void EnergyFunctional::resubstituteF_MT(const VecX &x, shared_ptr<CalibHessian> 
         for (int k = 0; k < 8; k++) h->step[k] = -x[CPARS + 8 * h->idx + k];
         h->step[8] = h->step[9] = 0;
     }
-    std::vector<float> step(ptPtr_.size());
+    std::vector<float> step(loaded_.pts.size());
     if (ldso_ba_resubstitute(ctx_, 0, x.data(), currentLambda_, step.data())) {
         fail("ldso_ba_resubstitute");
         return;
     }
-    for (size_t q = 0; q < ptPtr_.size(); q++) ptPtr_[q]->step = step[q];
+    for (size_t q = 0; q < step.size(); q++) loaded_.pts[q]->step = step[q];
 }
 
 }  // namespace ldso_amd

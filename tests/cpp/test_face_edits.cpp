@@ -9,7 +9,10 @@
 // flagged OUTLIER and removed (dropPointsF), then optimize(1) -- an edit on top of an edit, after the
 // device loop stepped the points.  Frame states, energies, inverse depths, HM and bM must be
 // bit-identical between the two;
-// the incremental face must have applied edits and fallen back on none.
+// the incremental face must have applied edits and fallen back on none.  The same comparison once
+// more with LDSO_BA_TUNE_ITEM_ORDER 2 on both faces, under which the library refuses every edit: the
+// incremental face falls back to the reload each time, the third time with the residuals' read-back
+// still deferred, and must stay bit-identical.
 //
 //   test_face_edits --cpu   the switch and its counters without a device
 //   test_face_edits         the GPU run
@@ -21,7 +24,9 @@ struct EditTrace : Trace {
     long applied = -1, fallen = -1;
 };
 
-static EditTrace drive_edits(const Synth &S, bool incremental) {
+// itemOrder: LDSO_BA_TUNE_ITEM_ORDER of the face's context, set before the first pass (2: the library
+// refuses every edit when it plans it, before anything is launched)
+static EditTrace drive_edits(const Synth &S, bool incremental, int itemOrder) {
     EditTrace T;
     const char *tag = incremental ? "incremental" : "reload";
     const int n0 = S.N - 1;
@@ -31,6 +36,8 @@ static EditTrace drive_edits(const Synth &S, bool incremental) {
     if (!ef->ok()) return T;
     CHECK(!ef->incrementalEdits(), "incremental edits are off by default");
     ef->setIncrementalEdits(incremental);
+    CHECK(ldso_ba_set_tuning(ef->context(), LDSO_BA_TUNE_ITEM_ORDER, itemOrder) == 0, "%s item order %d: %s", tag, itemOrder,
+          ldso_ba_last_error());
     G.insertInto(*ef);
     ldso_ba_opt_settings all_its = LDSO_BA_OPT_SETTINGS_INIT;
     all_its.th_opt_iterations = 0.0f;
@@ -102,11 +109,10 @@ static EditTrace drive_edits(const Synth &S, bool incremental) {
     return T;
 }
 
-static void gpu_edit_tests() {
-    Synth S(6, 300, 160, 120, 11);
-    const EditTrace A = drive_edits(S, true), B = drive_edits(S, false);
+// both faces over the same keyframes: everything they compute is bit-identical
+static bool same_results(const EditTrace &A, const EditTrace &B) {
     CHECK(A.ok && B.ok, "both faces ran");
-    if (!A.ok || !B.ok) return;
+    if (!A.ok || !B.ok) return false;
     CHECK(A.energies.size() == B.energies.size(), "energy count");
     for (size_t i = 0; i < A.energies.size() && i < B.energies.size(); i++)
         CHECK(std::memcmp(A.energies[i].data(), B.energies[i].data(), sizeof(Vec3)) == 0,
@@ -117,11 +123,29 @@ static void gpu_edit_tests() {
     CHECK(same_bits(A.idepth, B.idepth), "point inverse depths bit-identical");
     CHECK(same_bits(A.HM, B.HM), "HM bit-identical");
     CHECK(same_bits(A.bM, B.bM), "bM bit-identical");
-    std::printf("incremental face: %ld edits applied, %ld fallen back; reload face: %ld, %ld\n", A.applied, A.fallen, B.applied,
-                B.fallen);
-    CHECK(A.applied >= 2, "the incremental face edited the window (%ld)", A.applied);
-    CHECK(A.fallen == 0, "no edit fell back (%ld): %s", A.fallen, ldso_ba_last_error());
-    CHECK(B.applied == 0 && B.fallen == 0, "the reload face edits nothing");
+    return true;
+}
+
+static void gpu_edit_tests() {
+    Synth S(6, 300, 160, 120, 11);
+    const EditTrace A = drive_edits(S, true, 0), B = drive_edits(S, false, 0);
+    if (same_results(A, B)) {
+        std::printf("incremental face: %ld edits applied, %ld fallen back; reload face: %ld, %ld\n", A.applied, A.fallen,
+                    B.applied, B.fallen);
+        CHECK(A.applied >= 2, "the incremental face edited the window (%ld)", A.applied);
+        CHECK(A.fallen == 0, "no edit fell back (%ld): %s", A.fallen, ldso_ba_last_error());
+        CHECK(B.applied == 0 && B.fallen == 0, "the reload face edits nothing");
+    }
+    // item order 2: every edit is refused and the window reloaded instead; the third change (dropPointsF
+    // after optimize(2)) is refused with the read-back of the residuals still deferred
+    const EditTrace C = drive_edits(S, true, 2), D = drive_edits(S, false, 2);
+    if (same_results(C, D)) {
+        std::printf("item order 2: incremental face: %ld edits applied, %ld fallen back; reload face: %ld, %ld\n", C.applied,
+                    C.fallen, D.applied, D.fallen);
+        CHECK(C.applied == 0 && C.fallen >= 2, "every edit was refused and fell back (%ld applied, %ld fallen back)", C.applied,
+              C.fallen);
+        CHECK(D.applied == 0 && D.fallen == 0, "the reload face edits nothing");
+    }
 }
 
 static void cpu_edit_tests() {
