@@ -134,7 +134,7 @@ class FlagParams(C.Structure):
 
 def source_sha256() -> str | None:
     """sha256 over the sources libldso_ba.so is built from (ldso_amd/csrc, include/ldso_ba.h,
-    include/ldso_ct.h): the identity of a build that survives a rebuild on another machine (the .so
+    include/ldso_ct.h, include/ldso_lc.h): the identity of a build that survives a rebuild on another machine (the .so
     bytes do not)."""
     import glob
     import hashlib
@@ -144,7 +144,7 @@ def source_sha256() -> str | None:
                    glob.glob(os.path.join(root, "ldso_amd", "csrc", "*.h")) +
                    glob.glob(os.path.join(root, "ldso_amd", "csrc", "*.cpp")) +
                    [os.path.join(root, "ldso_amd", "csrc", "Makefile"), os.path.join(root, "include", "ldso_ba.h"),
-                    os.path.join(root, "include", "ldso_ct.h")])
+                    os.path.join(root, "include", "ldso_ct.h"), os.path.join(root, "include", "ldso_lc.h")])
     h = hashlib.sha256()
     try:
         for f in files:
@@ -415,6 +415,37 @@ CT_ABI = [
     ("ldso_ct_num_kernels", C.c_int32, []),
 ]
 
+# ldso_lc_feature / _match / _projection (include/ldso_lc.h): the loop closer's records
+LC_ABI_VERSION = 1
+LC_FEATURE_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("angle", "<f4"), ("inv_d", "<f4"), ("is_corner", "<i4"),
+                             ("usable", "<i4"), ("descriptor", "u1", (32,))])
+LC_MATCH_DTYPE = np.dtype([("index1", "<i4"), ("index2", "<i4"), ("dist", "<i4")])
+LC_PROJECTION_DTYPE = np.dtype([("index_cand", "<i4"), ("index_cur", "<i4"), ("dist", "<i4"), ("reserved_", "<i4"),
+                                ("p_ref", "<f8", (3,)), ("p_curr", "<f8", (3,)), ("pixel", "<f8", (2,))])
+assert LC_FEATURE_DTYPE.itemsize == 56 and LC_MATCH_DTYPE.itemsize == 12 and LC_PROJECTION_DTYPE.itemsize == 80
+
+# (name, restype, argtypes) of every entry point declared in include/ldso_lc.h (loop closing's matching)
+LC_ABI = [
+    ("ldso_lc_abi_version", C.c_int, []),
+    ("ldso_lc_create", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    ("ldso_lc_destroy", None, [C.c_void_p]),
+    ("ldso_lc_keyframe_put", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    ("ldso_lc_keyframe_put_tracker", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    ("ldso_lc_keyframe_update", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, f32p, i32p]),
+    ("ldso_lc_keyframe_set_bow", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, i32p, i32p, i32p]),
+    ("ldso_lc_keyframe_get", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, i32p]),
+    ("ldso_lc_keyframe_drop", C.c_int, [C.c_void_p, C.c_int64]),
+    ("ldso_lc_search_brute_force", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, i32p]),
+    ("ldso_lc_search_brute_force_many", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, i64p, C.c_int32, i32p, i32p, i32p]),
+    ("ldso_lc_search_by_bow", C.c_int,
+     [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_int32, C.c_void_p, i32p]),
+    ("ldso_lc_make_idepth_map_ba", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, f32p]),
+    ("ldso_lc_make_idepth_map", C.c_int, [C.c_void_p, C.c_int32, f32p]),
+    ("ldso_lc_get_idepth_map", C.c_int, [C.c_void_p, f32p]),
+    ("ldso_lc_search_by_projection", C.c_int,
+     [C.c_void_p, C.c_int64, C.c_int64, f32p, f64p, C.c_float, C.c_int32, C.c_int32, C.c_void_p, i32p]),
+]
+
 _lib = None
 _synth = None
 
@@ -428,13 +459,16 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(make -C ldso_amd/csrc). The HIP path has no CPU fallback.")
         L = C.CDLL(LIB_PATH)
-        for name, res, args in ABI + CT_ABI:
+        for name, res, args in ABI + CT_ABI + LC_ABI:
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
         if L.ldso_ba_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH} has ABI {L.ldso_ba_abi_version()}, these bindings expect {ABI_VERSION}: "
                                "rebuild it (make -C ldso_amd/csrc)")
+        if L.ldso_lc_abi_version() != LC_ABI_VERSION:
+            raise RuntimeError(f"{LIB_PATH} has loop-closing ABI {L.ldso_lc_abi_version()}, these bindings expect "
+                               f"{LC_ABI_VERSION}: rebuild it (make -C ldso_amd/csrc)")
         _lib = L
     return _lib
 

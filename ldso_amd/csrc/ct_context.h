@@ -88,6 +88,7 @@ struct ldso_ct_ctx {
     DevBuf<int4> d_cor_pattern;
     CorUmax cor_umax{};
     bool cor_init = false;
+    int cor_n = -1;  // features of the last detection whose records d_cor_feat / d_cor_out hold; -1: none
     DevBuf<int> d_cor_cell;               // [cells] pick counts, then [cells] their exclusive prefix
     DevBuf<CorSlot> d_cor_slot, d_cor_feat;  // the picks per cell; the features in output order
     DevBuf<int> d_cor_corner, d_cor_cnt;

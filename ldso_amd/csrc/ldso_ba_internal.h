@@ -145,6 +145,18 @@ struct CtSelectionView {
 };
 int ct_selection_view(const ldso_ct_ctx *ct, CtSelectionView *out);
 
+// The tracker's last corner detection as ldso_lc_keyframe_put_tracker reads it (the loop closer's translation
+// unit does not see ldso_ct_ctx): the features in output order, resident on the tracker's device.
+struct CtCornersView {
+    const int *pixel;     // feature i: x at pixel[i * pixel_stride], y behind it
+    int pixel_stride;     // ints between two features
+    const void *records;  // ldso_ct_feature [n]: score, angle, corner flag, descriptor
+    int n;                // -1: no detection yet, or the last one's capacity did not hold every record
+    int width, height, device;
+    void *stream;
+};
+int ct_corners_view(const ldso_ct_ctx *ct, CtCornersView *out);
+
 int frame_precalc(int N, const ldso_ba_frame_state *fr, const float calib[4], float *out);
 int set_adjoints(int N, const ldso_ba_frame_state *fr, double *adH, double *adT, double *cPrior);
 int frame_take_data(int N, const ldso_ba_frame_state *fr, float mode_a, float mode_b, double *prior, double *delta,

@@ -63,6 +63,22 @@ int ldso_ba::ct_selection_view(const ldso_ct_ctx *c, ldso_ba::CtSelectionView *o
     return 0;
 }
 
+// the loop closer's view of the last corner detection (ldso_lc_keyframe_put_tracker)
+int ldso_ba::ct_corners_view(const ldso_ct_ctx *c, ldso_ba::CtCornersView *out) {
+    if (!c || !out) return fail(-1, "null argument");
+    static_assert(sizeof(CorSlot) == 4 * sizeof(int) && offsetof(CorSlot, x) == 0 && offsetof(CorSlot, y) == sizeof(int),
+                  "CtCornersView reads x, y at the start of a CorSlot");
+    out->pixel = reinterpret_cast<const int *>(c->d_cor_feat.p);
+    out->pixel_stride = sizeof(CorSlot) / sizeof(int);
+    out->records = c->d_cor_out.p;
+    out->n = c->cor_n;
+    out->width = c->pyr.w;
+    out->height = c->pyr.h;
+    out->device = c->device;
+    out->stream = (void *)c->stream;
+    return 0;
+}
+
 namespace {
 
 // one launch on the context's stream into kernel-timing slot `slot`
@@ -718,6 +734,7 @@ int ldso_ct_detect_corners(ldso_ct_ctx *c, int32_t n_features, int32_t host, int
     const int ncells = G.ncx * G.ncy;
     int32_t stats[LDSO_CT_CORNER_STATS] = {G.g, G.k, 0, 0, 0, 0};
     *n_out = 0;
+    c->cor_n = -1;
     if (ncells > 0) {
         // every feature slot the grid has (each cell full of candidates), whatever the image holds
         const int n_slots = ncells * G.kk, cap = std::min(capacity, n_slots);
@@ -749,6 +766,7 @@ int ldso_ct_detect_corners(ldso_ct_ctx *c, int32_t n_features, int32_t host, int
         *n_out = hc[kCorCntFeatures];
     }
     const int n = *n_out;
+    c->cor_n = n <= capacity ? n : -1;  // the device holds a record per feature only when they all fitted
     if (stats_out) std::memcpy(stats_out, stats, sizeof stats);
     if (n > capacity) return fail(-1, "capacity below the number of features (see *n_out)");
     if (n > 0) {
