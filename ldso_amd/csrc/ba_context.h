@@ -67,7 +67,7 @@ struct FrameStore {
     std::vector<int64_t> id;
     std::vector<unsigned long long> seq;
     unsigned long long next_seq = 1;
-    Event ev_prod, ev_cons;  // producer -> ingest, ingest -> producer's next write
+    StreamBorrow borrow;  // producer -> ingest, ingest -> producer's next write
     float4 *slot(int s) const { return d_store.p + (size_t)s * lay.frame_stride; }
     // slot of a resident frame id, or -1
     int find(int64_t frame_id) const {
@@ -141,7 +141,7 @@ struct ldso_ba_ctx {
     FrameStore store;
     GraphBuf<ldso_ct_immature> d_act_in;  // point activation staging (ldso_ba_activate_points)
     GraphBuf<ldso_ba_activation> d_act_out;
-    Event act_ev_a, act_ev_b;  // ldso_ba_activate_points_tracker: tracker -> k_activate, k_activate -> tracker
+    StreamBorrow act_borrow;  // ldso_ba_activate_points_tracker: tracker -> k_activate, k_activate -> tracker
     GraphBuf<float> d_precalc, d_frame_th, d_pt_data, d_pt_out, d_pt_step;
     GraphBuf<double> d_adH, d_adT;
     GraphBuf<int> d_rs_slot, d_pt_nres, d_pair_win, d_frame_win, d_pt_host;
@@ -234,7 +234,7 @@ struct ldso_ba_ctx {
     ldso_ba::OldWindow flag_map;
     int flag_map_win = -1;
     // ldso_ba_load_marginalization_device, on the marginalisation context: parent -> gather, gather -> parent
-    Event mg_ev_a, mg_ev_b;
+    StreamBorrow mg_borrow;
     int64_t xfer[4] = {0, 0, 0, 0};  // ldso_ba_transfer_stats
     // timing-only events: no system-scope fence (its L2 write-back and invalidate would be timed, and
     // would slow the kernel after the start event)

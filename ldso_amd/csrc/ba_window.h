@@ -241,8 +241,6 @@ int place_store_frames(ldso_ba_ctx *c, const std::vector<int> &fslot) {
 // whatever that stream is given later -- a pass, an edit that swaps the arrays -- waits for the gather.
 // F: the load walk's parameters (newstate and R; its fills are load_apply's).
 int marg_gather(ldso_ba_ctx *c, const ldso_ba_ctx *parent, int parent_win, const EditParams &F) {
-    int rc;
-    if ((rc = c->mg_ev_a.ensure(hipEventDisableTiming)) || (rc = c->mg_ev_b.ensure(hipEventDisableTiming))) return rc;
     const WinDev &pw = parent->wd[parent_win];
     EditParams E = F;
     E.n_fill = 0;
@@ -267,17 +265,15 @@ int marg_gather(ldso_ba_ctx *c, const ldso_ba_ctx *parent, int parent_win, const
     E.P = c->P_tot;
     E.scale_prior = 1;
     E.prior_fac = kIdepthFixPriorMargFac;
-    HIP_TRY(hipEventRecord(c->mg_ev_a.e, parent->stream));
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->mg_ev_a.e, 0));
+    // read the parent's window behind what its stream holds now; its later work waits for the read
+    if (int rc = c->mg_borrow.begin(c->stream, parent->stream)) return rc;
     const size_t work = std::max<size_t>((size_t)E.R, (size_t)E.P * kPtVec);
     if (work) {
         const int nb = (int)std::min<size_t>(1024, (work + 255) / 256);
         k_edit_gather<<<nb, 256, 0, c->stream>>>(E);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(c->mg_ev_b.e, c->stream));
-    HIP_TRY(hipStreamWaitEvent(parent->stream, c->mg_ev_b.e, 0));
-    return 0;
+    return c->mg_borrow.end(c->stream, parent->stream);
 }
 
 // parent != nullptr: a marginalisation context over `ws[0]` whose frames are the parent's window

@@ -1,6 +1,7 @@
-// hip_owning.h -- what the host side of both translation units (ldso_ba.hip, ldso_ct.hip) builds its
-// contexts from: fail / HIP_TRY, the owning device and pinned buffers, the owning event, and the kernel
-// timer.  Every member of a context frees what it owns when the context is deleted.
+// hip_owning.h -- what the host side of the three translation units (ldso_ba.hip, ldso_ct.hip,
+// ldso_lc.hip) builds its contexts from: fail / HIP_TRY, the owning device and pinned buffers, the
+// owning event, StreamBorrow (the one place where two contexts' streams are ordered with each other),
+// and the kernel timer.  Every member of a context frees what it owns when the context is deleted.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -113,6 +114,34 @@ struct Event {
     }
     int ensure(unsigned flags) {
         if (!e) HIP_TRY(hipEventCreateWithFlags(&e, flags));
+        return 0;
+    }
+    void release() {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+};
+
+// Reading another context's device memory on my stream: between begin and end, what is enqueued on
+// `mine` runs behind everything `theirs` holds at begin, and whatever `theirs` is given after end runs
+// behind it.  The two events are created by the first begin, both or neither.  Not for use inside a
+// stream capture: event creation is not captured.
+struct StreamBorrow {
+    Event taken, given;  // recorded on theirs at begin; on mine at end
+    int begin(hipStream_t mine, hipStream_t theirs) {
+        int rc;
+        if ((rc = taken.ensure(hipEventDisableTiming)) || (rc = given.ensure(hipEventDisableTiming))) {
+            taken.release();
+            given.release();
+            return rc;
+        }
+        HIP_TRY(hipEventRecord(taken.e, theirs));
+        HIP_TRY(hipStreamWaitEvent(mine, taken.e, 0));
+        return 0;
+    }
+    int end(hipStream_t mine, hipStream_t theirs) {
+        HIP_TRY(hipEventRecord(given.e, mine));
+        HIP_TRY(hipStreamWaitEvent(theirs, given.e, 0));
         return 0;
     }
 };

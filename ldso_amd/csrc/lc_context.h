@@ -59,5 +59,5 @@ struct ldso_lc_ctx {
     DevBuf<float4> d_contrib;
     PinBuf<float4> h_contrib;
     bool have_map = false;
-    Event ev_a, ev_b;  // order another context's stream with this one
+    StreamBorrow borrow;  // the tracker's detection, the BA pass's arrays
 };

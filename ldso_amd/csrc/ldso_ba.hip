@@ -47,7 +47,7 @@
 //   which ldso_ba_load_marginalization_device points at the parent's arrays), k_flag.h (ldso_ba_flag_points)
 //                     the 28 non-template kernels by stage, included below in the order the kernels have
 //                     always been defined in
-//   hip_owning.h      shared with ldso_ct.hip: fail / HIP_TRY, the owning buffers and events, KernelTimer
+//   hip_owning.h      shared with ldso_ct.hip and ldso_lc.hip: fail / HIP_TRY, the owning buffers and events, StreamBorrow, KernelTimer
 //   ba_context.h      the timing slots, the environment switches (read_switches), the allocation
 //                     generation, the frame store, struct ldso_ba_ctx
 //   ba_launch.h       staged uploads, timed launches, image staging, the parameter fillers and the
@@ -308,8 +308,8 @@ void *ldso_ba_stream(ldso_ba_ctx *c) { return c ? (void *)c->stream : nullptr; }
 
 namespace {
 // Device -> slot on the context stream, ordered by events and never by the host: the ingest waits for
-// what the producer's stream holds now (ev_prod), and whatever that stream is given later -- the
-// producer's next overwrite of its buffers -- waits for the ingest (ev_cons).  The slot itself is
+// what the producer's stream holds now, and whatever that stream is given later -- the producer's
+// next overwrite of its buffers -- waits for the ingest (StreamBorrow).  The slot itself is
 // only ever read and written on the context stream, so stream order keeps the write behind any load
 // still copying out of it.
 int store_ingest_device(ldso_ba_ctx *c, int64_t id, const float *inten, const void *texels, hipStream_t prod) {
@@ -323,8 +323,7 @@ int store_ingest_device(ldso_ba_ctx *c, int64_t id, const float *inten, const vo
     if (l.mode == 3 && !inten)
         return fail(-1, "image layout 3 stores intensities: the device source must give the intensity plane");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventRecord(S.ev_prod.e, prod));
-    HIP_TRY(hipStreamWaitEvent(c->stream, S.ev_prod.e, 0));
+    if ((rc = S.borrow.begin(c->stream, prod))) return rc;
     const int nb = (int)((l.frame_stride + 255) / 256);  // a thread per float4 of the slot, both layouts
     if (l.mode == 3)
         k_ingest_intensity<<<nb, 256, 0, c->stream>>>(inten, S.slot(slot), l.width, l.height, l.tiles_per_row * 8, l.padded_h);
@@ -332,8 +331,7 @@ int store_ingest_device(ldso_ba_ctx *c, int64_t id, const float *inten, const vo
         k_ingest_texels<<<nb, 256, 0, c->stream>>>(static_cast<const float4 *>(texels), S.slot(slot), l.width, l.height,
                                                    l.tiles_per_row, l.padded_h);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(S.ev_cons.e, c->stream));
-    HIP_TRY(hipStreamWaitEvent(prod, S.ev_cons.e, 0));
+    if ((rc = S.borrow.end(c->stream, prod))) return rc;
     c->xfer[1] += (int64_t)l.slot_bytes();
     S.commit(slot, id);
     c->xfer[3]++;
@@ -515,7 +513,6 @@ int ldso_ba_frames_reserve(ldso_ba_ctx *c, int32_t capacity, int32_t width, int3
     if (rc) return rc;
     if ((rc = image_staging(c, S.lay.npix()))) return rc;
     if ((rc = c->pin_img.ensure(S.lay.npix() * 3 * sizeof(float) + 64))) return rc;
-    if ((rc = S.ev_prod.ensure(hipEventDisableTiming)) || (rc = S.ev_cons.ensure(hipEventDisableTiming))) return rc;
     S.id.assign((size_t)capacity, 0);
     S.seq.assign((size_t)capacity, 0ull);
     S.cap = capacity;
@@ -812,6 +809,23 @@ int comm_exchange(ldso_ba_ctx *c, bool accumulate, int pass, const Switches &sw)
             chain_here ? c->win_nid() : nullptr, stop, pass);
     });
 }
+
+// k_activate's argument for n immature records at pts (the context's staging or the tracker's selection)
+ActParams act_params(ldso_ba_ctx *c, int win, const ldso_ct_immature *pts, int n, int min_obs) {
+    ActParams A;
+    A.wins = c->d_wins.p;
+    A.img = c->images();
+    A.precalc = c->d_precalc.p;
+    A.pts = pts;
+    A.out = c->d_act_out.p;
+    A.frame_stride = c->img.frame_stride;
+    A.tpr = c->img.tiles_per_row;
+    A.img_mode = c->img.mode;
+    A.win = win;
+    A.n = n;
+    A.min_obs = min_obs;
+    return A;
+}
 }  // namespace
 
 extern "C" {
@@ -1029,18 +1043,7 @@ int ldso_ba_activate_points(ldso_ba_ctx *c, int32_t win, int32_t n, const ldso_c
         if (rc) return rc;
     }
     HIP_TRY(hipMemcpyAsync(c->d_act_in.p, pts, (size_t)n * sizeof(ldso_ct_immature), hipMemcpyHostToDevice, c->stream));
-    ActParams A;
-    A.wins = c->d_wins.p;
-    A.img = c->images();
-    A.precalc = c->d_precalc.p;
-    A.pts = c->d_act_in.p;
-    A.out = c->d_act_out.p;
-    A.frame_stride = c->img.frame_stride;
-    A.tpr = c->img.tiles_per_row;
-    A.img_mode = c->img.mode;
-    A.win = win;
-    A.n = n;
-    A.min_obs = min_obs;
+    const ActParams A = act_params(c, win, c->d_act_in.p, n, min_obs);
     int rc = timed_launch(c, kSlotActivate, c->stream, [&] { k_activate<<<(n + 3) / 4, 256, 0, c->stream>>>(A); });
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, c->d_act_out.p, (size_t)n * sizeof(ldso_ba_activation), hipMemcpyDeviceToHost,
@@ -1064,27 +1067,13 @@ int ldso_ba_activate_points_tracker(ldso_ba_ctx *c, int32_t win, const ldso_ct_c
     HIP_TRY(hipSetDevice(c->device));
     if ((size_t)n > c->d_act_out.n || !c->d_act_out.p)
         if ((rc = c->d_act_out.alloc(n))) return rc;
-    if ((rc = c->act_ev_a.ensure(hipEventDisableTiming)) || (rc = c->act_ev_b.ensure(hipEventDisableTiming))) return rc;
     // read the records behind what the tracker's stream holds now; its later work waits for the read
     hipStream_t ts = static_cast<hipStream_t>(V.stream);
-    HIP_TRY(hipEventRecord(c->act_ev_a.e, ts));
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->act_ev_a.e, 0));
-    ActParams A;
-    A.wins = c->d_wins.p;
-    A.img = c->images();
-    A.precalc = c->d_precalc.p;
-    A.pts = static_cast<const ldso_ct_immature *>(V.records);
-    A.out = c->d_act_out.p;
-    A.frame_stride = c->img.frame_stride;
-    A.tpr = c->img.tiles_per_row;
-    A.img_mode = c->img.mode;
-    A.win = win;
-    A.n = n;
-    A.min_obs = min_obs;
+    if ((rc = c->act_borrow.begin(c->stream, ts))) return rc;
+    const ActParams A = act_params(c, win, static_cast<const ldso_ct_immature *>(V.records), n, min_obs);
     rc = timed_launch(c, kSlotActivate, c->stream, [&] { k_activate<<<(n + 3) / 4, 256, 0, c->stream>>>(A); });
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(c->act_ev_b.e, c->stream));
-    HIP_TRY(hipStreamWaitEvent(ts, c->act_ev_b.e, 0));
+    if ((rc = c->act_borrow.end(c->stream, ts))) return rc;
     HIP_TRY(hipMemcpyAsync(out, c->d_act_out.p, (size_t)n * sizeof(ldso_ba_activation), hipMemcpyDeviceToHost,
                            c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

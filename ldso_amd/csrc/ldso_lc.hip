@@ -140,8 +140,7 @@ int ldso_lc_create(int32_t device, int32_t width, int32_t height, int32_t max_ke
         (rc = c->h_floats.ensure(F)) || (rc = c->d_ints.alloc(F)) || (rc = c->d_floats.alloc(F)) ||
         (rc = c->d_ckey.alloc(F)) || (rc = c->d_skey.alloc(F)) || (rc = c->idx_status.ensure(2)) ||
         (rc = c->idx_corner.ensure(F)) || (rc = c->h_pairs.ensure(max_keyframes)) || (rc = c->d_matches.alloc(F)) ||
-        (rc = c->d_proj.alloc(F)) || (rc = c->count.ensure(1)) || (rc = c->d_map.alloc((size_t)width * height)) ||
-        (rc = c->ev_a.ensure(hipEventDisableTiming)) || (rc = c->ev_b.ensure(hipEventDisableTiming))) {
+        (rc = c->d_proj.alloc(F)) || (rc = c->count.ensure(1)) || (rc = c->d_map.alloc((size_t)width * height))) {
         const std::string why = ldso_ba::last_error();
         ldso_lc_destroy(c);
         return fail(rc, why);
@@ -197,13 +196,11 @@ int ldso_lc_keyframe_put_tracker(ldso_lc_ctx *c, int64_t kf, const ldso_ct_ctx *
     if (n > 0) {
         // read the detection behind what the tracker's stream holds now; its later work waits for the read
         hipStream_t ts = static_cast<hipStream_t>(V.stream);
-        HIP_TRY(hipEventRecord(c->ev_a.e, ts));
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_a.e, 0));
+        if ((rc = c->borrow.begin(c->stream, ts))) return rc;
         k_lc_from_tracker<<<lc_blocks(n), kLcThreads, 0, c->stream>>>(
             V.pixel, V.pixel_stride, static_cast<const ldso_ct_feature *>(V.records), n, c->d_feat.p + (size_t)slot * c->F);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->ev_b.e, c->stream));
-        HIP_TRY(hipStreamWaitEvent(ts, c->ev_b.e, 0));
+        if ((rc = c->borrow.end(c->stream, ts))) return rc;
     }
     return lc_commit(c, kf, slot, n);
 }
@@ -378,14 +375,12 @@ int ldso_lc_make_idepth_map_ba(ldso_lc_ctx *c, const ldso_ba_ctx *ba, int32_t wi
         }
         // read the pass's arrays behind what the BA stream holds now; its later work waits for the read
         hipStream_t bs = static_cast<hipStream_t>(V.stream);
-        HIP_TRY(hipEventRecord(c->ev_a.e, bs));
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_a.e, 0));
+        if ((rc = c->borrow.begin(c->stream, bs))) return rc;
         HIP_TRY(hipMemsetAsync(c->d_contrib.p, 0xFF, (size_t)n * sizeof(float4), c->stream));  // NaN: no contribution
         LcGatherParams G{V.center, V.plane_stride, V.state, V.tgt, V.slot, c->d_contrib.p, V.R, V.P, V.rec_base, target_frame};
         k_lc_map_gather<<<lc_blocks(V.R), kLcThreads, 0, c->stream>>>(G);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->ev_b.e, c->stream));
-        HIP_TRY(hipStreamWaitEvent(bs, c->ev_b.e, 0));
+        if ((rc = c->borrow.end(c->stream, bs))) return rc;
     }
     if ((rc = lc_write_map(c, n))) return rc;
     if (map_out) HIP_TRY(hipMemcpyAsync(map_out, c->d_map.p, c->d_map.bytes(), hipMemcpyDeviceToHost, c->stream));

@@ -48,6 +48,12 @@ int main() {
     CHECK(d.alloc(0) == 0 && d.p == nullptr && d.n == 0);  // an empty buffer is not an error
     Event ev;
     CHECK(ev.ensure(hipEventDisableTiming) < 0 && ev.e == nullptr);
+    // a borrow that cannot create its events refuses, holds neither, and refuses again
+    StreamBorrow sb;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        CHECK(sb.begin(nullptr, nullptr) < 0);
+        CHECK(sb.taken.e == nullptr && sb.given.e == nullptr);
+    }
     std::printf("%d failure(s)\n", failures);
     return failures ? 1 : 0;
 }
