@@ -54,6 +54,7 @@ def lib():
             "oracle_iteration": (C.c_int, [C.c_void_p, f64p]),
             "oracle_get_residuals": (None, [C.c_void_p, i8p, i8p, f32p, f32p, f32p, u8p, f32p, f32p]),
             "oracle_get_jacobians": (None, [C.c_void_p, f32p]),
+            "oracle_get_jabf_lin": (None, [C.c_void_p, f32p]),
             "oracle_get_points": (None, [C.c_void_p, f32p, f32p, f32p, f32p, f32p, f32p]),
             "oracle_get_frame_energy_th": (None, [C.c_void_p, f32p]),
             "oracle_solve_system": (C.c_int, [C.c_int, C.c_int, C.c_double] + [f64p] * 9 + [C.c_int, f64p]),
@@ -129,6 +130,7 @@ class OracleWindow:
         rc = lib().oracle_update(self._h, C.byref(s))
         window._keep = []
         assert rc == 0
+        self.window = window  # same structure (oracle_update takes frames, adjoints and point data from it)
 
     def reset_oob(self):
         lib().oracle_reset_oob(self._h)
@@ -175,6 +177,13 @@ class OracleWindow:
     def jacobians(self) -> np.ndarray:
         out = np.zeros((self.window.n_residuals, 78), np.float32)
         lib().oracle_get_jacobians(self._h, _p(out, f32p))
+        return out
+
+    def jabf_lin(self) -> np.ndarray:
+        """[R, 16]: JabF as linearize formed it, before a fixed affine mode (setting_affineOptModeA / B < 0)
+        zeroes it in jacobians(); JabJIdx and Jab2, hence HA and Hsc, are summed from these."""
+        out = np.zeros((self.window.n_residuals, 16), np.float32)
+        lib().oracle_get_jabf_lin(self._h, _p(out, f32p))
         return out
 
     def points(self) -> dict:

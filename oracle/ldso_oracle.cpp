@@ -380,6 +380,9 @@ struct Residual {
     float centerProjectedTo[3] = {0, 0, 0};
     float res_toZeroF[8];
     float JpJdF[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // J.JabF as linearize forms it, before a fixed affine mode zeroes it (Residuals.cc:186-187): JabJIdx and
+    // Jab2, hence H, are summed from these.  Read back by the checker only (oracle_get_jabf_lin).
+    float JabF_lin[2][8] = {{0}};
     bool isLinearized = false;
     bool isActiveAndIsGoodNEW = false;
     float relBS = 0;
@@ -690,6 +693,8 @@ double linearize(oracle_window *ow, Residual &r) {
             J.JIdx[1][idx] = hitColor[2];
             J.JabF[0][idx] = drdA * hw;
             J.JabF[1][idx] = hw;
+            r.JabF_lin[0][idx] = J.JabF[0][idx];
+            r.JabF_lin[1][idx] = J.JabF[1][idx];
             JIdxJIdx_00 += hitColor[1] * hitColor[1];
             JIdxJIdx_11 += hitColor[2] * hitColor[2];
             JIdxJIdx_10 += hitColor[1] * hitColor[2];
@@ -1643,6 +1648,12 @@ void oracle_get_residuals(oracle_window *ow, int8_t *new_state, int8_t *state, f
             for (int i = 0; i < 8; i++) jpjdf[8 * k + i] = r.JpJdF[i];
         if (rel_bs) rel_bs[k] = r.relBS;
     }
+}
+
+void oracle_get_jabf_lin(oracle_window *ow, float *out) {
+    for (size_t k = 0; k < ow->res.size(); k++)
+        for (int a = 0; a < 2; a++)
+            for (int i = 0; i < 8; i++) out[16 * k + 8 * a + i] = ow->res[k].JabF_lin[a][i];
 }
 
 void oracle_get_jacobians(oracle_window *ow, float *out) {

@@ -58,6 +58,8 @@ void oracle_get_residuals(oracle_window *ow, int8_t *new_state, int8_t *state, f
 /* RawResidualJacobian dump per residual: resF[8], Jpdxi[2][6], Jpdc[2][4], Jpdd[2], JIdx[2][8],
  * JabF[2][8], JIdx2[4], JabJIdx[4], Jab2[4]  (= 78 floats) */
 void oracle_get_jacobians(oracle_window *ow, float *out78);
+// [R][16]: JabF as linearize formed it, before a fixed affine mode zeroes it (what JabJIdx / Jab2 were summed from)
+void oracle_get_jabf_lin(oracle_window *ow, float *out16);
 void oracle_get_points(oracle_window *ow, float *HdiF, float *bdSumF, float *idepth_hessian,
                        float *Hdd_acc, float *bd_acc, float *Hcd_acc);
 void oracle_get_frame_energy_th(oracle_window *ow, float *th);

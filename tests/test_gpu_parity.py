@@ -7,7 +7,9 @@ Bars (SURVEY.md §7 "Hard parts", BASELINE.json north_star):
     order with FMA contraction off;
   * linearizeAll energy: relative 1e-12 (double sums, different order);
   * stitched H, b (float accumulation reassociated on the GPU, then double): per 8x8 block
-    relative Frobenius error <= 1e-4 (the north star's tolerance is 1e-4 on the energy);
+    relative Frobenius error <= 1e-4 (the north star's tolerance is 1e-4 on the energy), and
+    elementwise within the rounding bound of tests/system_bound.py (both tiers) of the float64
+    normal equations rebuilt from the oracle's per-residual Jacobians;
   * solve: the product's solver matches the oracle's on the same system to 1e-9; end to end, x
     stays within 20x the system's float-rounding sensitivity envelope (see sensitivity());
   * resubstituted point steps: relative 1e-3 on the step vector.
@@ -16,6 +18,7 @@ import numpy as np
 import pytest
 
 import oracle
+import system_bound
 from ldso_amd import BAContext, synth
 
 pytestmark = pytest.mark.gpu
@@ -95,6 +98,7 @@ def compare_pass(ctx, ow, win_idx, e_cpu, s_cpu, check_system=True):
     assert block_errors(s_gpu["Hsc"], s_cpu["Hsc"], N) < BLOCK_TOL
     assert vec_block_errors(s_gpu["bA"], s_cpu["bA"], N) < BLOCK_TOL
     assert vec_block_errors(s_gpu["bsc"], s_cpu["bsc"], N) < BLOCK_TOL
+    system_bound.check_system(s_gpu, ow, s_cpu, f"window {win_idx}")
     np.testing.assert_array_equal(s_gpu["HL"], s_cpu["HL"])
     np.testing.assert_array_equal(s_gpu["bL"], s_cpu["bL"])
     return s_gpu
@@ -193,6 +197,10 @@ def test_caller_point_order_does_not_matter(built):
         assert block_errors(s2[k], s1[k], N) < BLOCK_TOL, k
     for k in ("bA", "bsc"):
         assert vec_block_errors(s2[k], s1[k], N) < BLOCK_TOL, k
+    # each side beside the float64 rebuild of the window (the same addends in either point order)
+    O, D, B, cnt = system_bound.oracle_reference(synth.make_window(**cfg))
+    system_bound.assert_elementwise(s1, O, D, B, cnt, "random order")
+    system_bound.assert_elementwise(s2, O, D, B, cnt, "image order")
     c1.close()
     c2.close()
 
@@ -286,6 +294,9 @@ def test_shards_sum_to_full(built):
         assert block_errors(tot, s_full[k], N) < BLOCK_TOL
     for k in ("bA", "bsc"):
         assert vec_block_errors(sum(p[k] for p in parts), s_full[k], N) < BLOCK_TOL
+    O, D, B, cnt = system_bound.oracle_reference(synth.make_window(**cfg))
+    system_bound.assert_elementwise(s_full, O, D, B, cnt, "full window")
+    system_bound.assert_elementwise({k: sum(p[k] for p in parts) for k in system_bound.KEYS}, O, D, B, cnt, "sum of 3 shards")
     for p in parts:
         np.testing.assert_array_equal(p["HL"], s_full["HL"])
         np.testing.assert_array_equal(p["bL"], s_full["bL"])
@@ -324,6 +335,9 @@ def test_s11_split_over_four_contexts(built):
         assert block_errors(sum(p[0][k] for p in parts), s_full[k], N) < BLOCK_TOL, k
     for k in ("bA", "bsc"):
         assert vec_block_errors(sum(p[0][k] for p in parts), s_full[k], N) < BLOCK_TOL, k
+    O, D, B, cnt = system_bound.oracle_reference(synth.make_window(**cfg))
+    system_bound.assert_elementwise(s_full, O, D, B, cnt, "S11")
+    system_bound.assert_elementwise({k: sum(p[0][k] for p in parts) for k in system_bound.KEYS}, O, D, B, cnt, "S11, sum of 4 shards")
     assert sum(p[1][2] for p in parts) == e_full[2]
     assert abs(sum(p[1][0] for p in parts) - e_full[0]) <= 1e-9 * abs(e_full[0])
     stride = max(strides)

@@ -87,6 +87,7 @@ def test_world2_exchange_of_device_buffers(built):
     import torch.multiprocessing as mp
 
     from ldso_amd import BAContext, synth
+    import system_bound
     from test_gpu_parity import BLOCK_TOL, block_errors, sensitivity, vec_block_errors
 
     world = 2
@@ -112,12 +113,15 @@ def test_world2_exchange_of_device_buffers(built):
     x2_full = full.solve(0, 2, 1e-5, ns)
     full.close()
     N = CFG["n_frames"]
+    O, D, B, cnt = system_bound.oracle_reference(synth.make_window(**CFG))
+    system_bound.assert_elementwise(s_full, O, D, B, cnt, "unsharded")
     for o in outs:
         s = o["system"]
         for k in ("HA", "Hsc"):
             assert block_errors(s[k], s_full[k], N) < BLOCK_TOL, k
         for k in ("bA", "bsc"):
             assert vec_block_errors(s[k], s_full[k], N) < BLOCK_TOL, k
+        system_bound.assert_elementwise(s, O, D, B, cnt, f"rank {o['rank']}")  # each side beside the unsharded rebuild
         np.testing.assert_array_equal(s["HL"], s_full["HL"])  # every rank has the priors
         np.testing.assert_array_equal(s["bL"], s_full["bL"])
         assert o["energy"][2] == e_full[2]

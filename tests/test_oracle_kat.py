@@ -18,14 +18,7 @@ import pytest
 
 import oracle
 from ldso_amd import synth
-
-J_OFF = dict(resF=0, Jpdxi=8, Jpdc=20, Jpdd=28, JIdx=30, JabF=46, JIdx2=62, JabJIdx=66, Jab2=70)
-
-
-def unpack_J(row):
-    o = J_OFF
-    return dict(resF=row[0:8], Jpdxi=row[8:20].reshape(2, 6), Jpdc=row[20:28].reshape(2, 4), Jpdd=row[28:30],
-                JIdx=row[30:46].reshape(2, 8), JabF=row[46:62].reshape(2, 8))
+from system_bound import J_OFF, unpack_J  # noqa: F401  (the per-residual Jacobian row's layout)
 
 
 WINDOWS = {

@@ -2,7 +2,8 @@
 contexts on device 0, each holding its run of the host-frame partition, with the exchange done by the
 test through the library's documented calls (tests/sharded.py), beside the oracle on the WHOLE
 window.  Bars are the project's own: per residual and per point bit for bit, the reduced system
-within test_gpu_parity.BLOCK_TOL per 8x8 block, the priors exact, #IN equal, the energy to 1e-9
+within test_gpu_parity.BLOCK_TOL per 8x8 block and elementwise within tests/system_bound.py's rounding
+bound of the whole window's float64 rebuild, the priors exact, #IN equal, the energy to 1e-9
 (test_s11_split_over_four_contexts' bar), the threshold bit for bit on every rank.
 tests/test_sharded_cases.py shows on the CPU that every case is well posed.
 
@@ -23,6 +24,7 @@ import pytest
 import oracle
 import ragged
 import sharded
+import system_bound
 from ldso_amd import _lib as L
 
 pytestmark = pytest.mark.gpu
@@ -62,6 +64,8 @@ def compare_sharded_pass(sh, ows, results, check_system=True, tag=""):
                 print(f"{tag} window {i}: reduced-system block errors", {k: f"{v:.2e}" for k, v in errs.items()})
             worst = max(worst, max(errs.values()))
             assert max(errs.values()) < BLOCK_TOL, (tag, i, r, errs)
+            if r == 0:  # the other ranks hold the same reduced system, bit for bit (below)
+                system_bound.check_system(s, ow, s_cpu, f"{tag} window {i}")
             np.testing.assert_array_equal(s["HL"], s_cpu["HL"])
             np.testing.assert_array_equal(s["bL"], s_cpu["bL"])
             for k in ("HA", "bA", "Hsc", "bsc"):  # one reduced system, on every rank
